@@ -5,15 +5,23 @@ over N GPUs (strong scaling, 256 / N per GPU).  At N > 1 the line also carries t
 as ``other_scaling_row``.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B | --global-batch G] [--dtype ...]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 A step = one forward of the whole hot path (conv_1 ... hGRU x8 ... fc_out) over B synthetic crops
 already resident in HBM.  Weights: synthetic (splitmix64 glorot stand-ins), generated on rank 0
 and broadcast ONCE over RCCL (xGMI) as one flat fp32 blob before timing.  Rank 0 prints one JSON
-line; value = all ranks' crops / max-over-ranks elapsed.  At N=1 the line also carries the parity
-of the measured path vs the float64 oracle, the CPU baseline, and "extras" (the other BASELINE
-configs: hierarchical regressor at batch 256, dense regressor, batch-1 end-to-end latency with the
-host CoM crop).
+line; value = all ranks' crops / max-over-ranks elapsed.
+
+A plain run does what the headline needs and no more: set up, warm up, time the K steps, write the
+outputs if ``--dump-outputs DIR`` is given (``DIR/pose.npy``: the [B, 69] float32 pose vectors the
+last timed step left in its output buffer; the inputs are seeded, so two builds can be compared
+output for output), print the line.  ``--full`` adds every other measurement to the line: the
+per-kernel HIP-event profile pass and the roofline, the measured HBM ceilings, at N > 1 the other
+scaling reading, and at N=1 the parity of the measured path vs the float64 oracle, the CPU baseline
+and "extras" (the other BASELINE configs: hierarchical regressor at batch 256, dense regressor,
+batch-1 end-to-end latency with the host CoM crop); ``--no-cpu-baseline`` / ``--no-parity`` /
+``--no-extras`` drop legs of a ``--full`` run.
 """
 import argparse
 import datetime
@@ -49,9 +57,15 @@ def parse():
     p.add_argument("--dtype", default="f32_fft", choices=["f32", "f32_split", "f32_fft", "bf16"],
                    help="hGRU eCRF conv path: exact fp32 MFMA direct, fp32-accurate f16x3 split "
                         "direct, fp32 FFT convolution, or the FFT path with bf16 spectral GEMMs")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-parity", action="store_true")
-    p.add_argument("--no-extras", action="store_true")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed to DIR/pose.npy "
+                        "([B, 69] float32; at N > 1 each rank writes DIR/pose_rank<r>.npy)")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline: per-kernel profile pass and roofline, HBM "
+                        "probe, other scaling reading (N > 1), CPU baseline, parity, extras")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    p.add_argument("--no-parity", action="store_true", help="with --full: skip the parity figures")
+    p.add_argument("--no-extras", action="store_true", help="with --full: skip the other configs")
     p.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                    help="torch.distributed backend for N > 1 (nccl = RCCL over xGMI)")
     return p.parse_args()
@@ -710,6 +724,63 @@ def main():
         return el
 
     elapsed = timed(depth, o0, out, args.steps, args.warmup)
+    if args.dump_outputs:   # what the last timed step left in its output buffer
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "pose.npy" if world == 1 else f"pose_rank{rank}.npy"),
+                out.cpu().numpy().astype(np.float32, copy=False))
+    fft = args.dtype in ("f32_fft", "bf16")
+    fft_loop = ctx.info("fft_loop")
+    value = gb * args.steps / elapsed
+    dev_list = []
+    if world > 1:   # which device each rank ran on (RCCL needs one rank per GPU; gloo rehearsals may share)
+        dl = [None] * world
+        dist.all_gather_object(dl, dev.index)
+        dev_list = dl
+    if strong:
+        metric = (f"depth-crops/sec hGRU-8T fwd @global batch {gb} over {world} GPU (strong scaling, "
+                  f"{crop}x{crop} crops)")
+    else:
+        metric = f"depth-crops/sec hGRU-8T fwd @batch{B} per GPU (weak scaling, {crop}x{crop} crops)"
+    rec = {
+        "metric": metric,
+        "value": round(value, 3),
+        "unit": "crops/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "strong" if strong else "weak",
+        "vs_baseline": None,
+        "dtype": {"f32": "f32", "f32_split": "f32 (f16x3 split MFMA, fp32 accumulate)",
+                  "f32_fft": "f32 (fp32 FFT convolution, fp32-accurate f16x3 spectral GEMM)",
+                  "bf16": "bf16 (bf16 spectra and hGRU maps, bf16 spectral / gate GEMMs, fp32 accumulate, fp32 FFTs and elementwise math)"}[args.dtype],
+        "data": "synthetic crops + synthetic weights (splitmix64 stand-ins; reference publishes none)",
+        "config": {"workload": f"hgru_pose.model.build fwd, T={T}, {crop}x{crop} crops, "
+                               + (f"global batch {gb} sharded over {world} GPU" if strong else f"batch {B} per GPU"),
+                   "global_batch": gb, "per_gpu_batch": B, "crop": crop,
+                   "timesteps": T,
+                   "parallelism": (f"dp{world} (contiguous batch shards, one {'RCCL' if args.backend == 'nccl' else 'gloo'} "
+                                   "weight broadcast before timing, no collective in the timed region)") if world > 1
+                   else "dp1 (single GPU, no collective)",
+                   "hgru_streams": (int(os.environ.get("MP_STREAMS", "2")) if fft else 1),
+                   "hgru_loop": {4: "four-step FFT loop (k_fft4.hip: 4 launches per timestep)",
+                                 6: "six-launch FFT loop (k_fft.hip)", 0: "direct conv"}[fft_loop]},
+        "ranks": dist.get_world_size() if world > 1 else 1,
+        "backend": (dist.get_backend() if world > 1 else "none (one process)"),
+        "devices": (dev_list if world > 1 else [dev.index]),
+        "weight_bcast_ms": round(bcast_s * 1e3, 3),
+        "weight_bcast_bytes": binfo.get("bytes"),
+        "weight_bcast_form": binfo.get("form"),
+        "src_sha": tree_stamp(),
+    }
+    if not args.full:   # the plain run ends here: the headline and what it was measured on
+        if rank == 0:
+            print(json.dumps(rec), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    # ---- everything below runs under --full only ----
     # the other scaling reading of the metric, after the timed region (N > 1 only): the strong row
     # (global batch 256 sharded) next to a weak headline, or the weak row (256 per GPU) next to a
     # strong headline
@@ -750,61 +821,15 @@ def main():
     conv15_flop = 2.0 * px * 15 * 15 * 64 * 64 * B            # algorithmic, per launch
     achieved_tf = conv15_flop / (conv_launch_ms * 1e-3) / 1e12
 
-    fft = args.dtype in ("f32_fft", "bf16")
-    fft_loop = ctx.info("fft_loop")
     kern = fft_kernels(ctx, B, px, prof_steps, args.dtype == "bf16") if fft else None
     hbm_meas = hbm_rates(dev) if fft else None   # after the timed region
-    value = gb * args.steps / elapsed
-    dev_list = []
-    if world > 1:   # which device each rank ran on (RCCL needs one rank per GPU; gloo rehearsals may share)
-        dl = [None] * world
-        dist.all_gather_object(dl, dev.index)
-        dev_list = dl
-    if strong:
-        metric = (f"depth-crops/sec hGRU-8T fwd @global batch {gb} over {world} GPU (strong scaling, "
-                  f"{crop}x{crop} crops)")
-    else:
-        metric = f"depth-crops/sec hGRU-8T fwd @batch{B} per GPU (weak scaling, {crop}x{crop} crops)"
-    rec = {
-        "metric": metric,
-        "value": round(value, 3),
-        "unit": "crops/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": "strong" if strong else "weak",
-        "vs_baseline": None,
-        "dtype": {"f32": "f32", "f32_split": "f32 (f16x3 split MFMA, fp32 accumulate)",
-                  "f32_fft": "f32 (fp32 FFT convolution, fp32-accurate f16x3 spectral GEMM)",
-                  "bf16": "bf16 (bf16 spectra and hGRU maps, bf16 spectral / gate GEMMs, fp32 accumulate, fp32 FFTs and elementwise math)"}[args.dtype],
-        "data": "synthetic crops + synthetic weights (splitmix64 stand-ins; reference publishes none)",
-        "config": {"workload": f"hgru_pose.model.build fwd, T={T}, {crop}x{crop} crops, "
-                               + (f"global batch {gb} sharded over {world} GPU" if strong else f"batch {B} per GPU"),
-                   "global_batch": gb, "per_gpu_batch": B, "crop": crop,
-                   "timesteps": T,
-                   "parallelism": (f"dp{world} (contiguous batch shards, one {'RCCL' if args.backend == 'nccl' else 'gloo'} "
-                                   "weight broadcast before timing, no collective in the timed region)") if world > 1
-                   else "dp1 (single GPU, no collective)",
-                   "hgru_streams": (int(os.environ.get("MP_STREAMS", "2")) if fft else 1),
-                   "hgru_loop": {4: "four-step FFT loop (k_fft4.hip: 4 launches per timestep)",
-                                 6: "six-launch FFT loop (k_fft.hip)", 0: "direct conv"}[fft_loop]},
-        "roofline": (fft_roofline(kern, args.dtype == "bf16", B, hbm_meas) if fft else
-                     roofline(args.dtype, achieved_tf, conv_launch_ms, na + nb, conv15_flop)),
-        "breakdown_ms_per_step": {"conv15": round((ms_a + ms_b) / prof_steps, 3),
-                                  "fc1": round(ms_fc / max(1, nfc), 3),
-                                  "backbone": round(ms_bb / max(1, nbb), 3)},
-        "ranks": dist.get_world_size() if world > 1 else 1,
-        "backend": (dist.get_backend() if world > 1 else "none (one process)"),
-        "devices": (dev_list if world > 1 else [dev.index]),
-        "weight_bcast_ms": round(bcast_s * 1e3, 3),
-        "weight_bcast_bytes": binfo.get("bytes"),
-        "weight_bcast_form": binfo.get("form"),
-    }
+    rec["roofline"] = (fft_roofline(kern, args.dtype == "bf16", B, hbm_meas) if fft else
+                       roofline(args.dtype, achieved_tf, conv_launch_ms, na + nb, conv15_flop))
+    rec["breakdown_ms_per_step"] = {"conv15": round((ms_a + ms_b) / prof_steps, 3),
+                                    "fc1": round(ms_fc / max(1, nfc), 3),
+                                    "backbone": round(ms_bb / max(1, nbb), 3)}
     if other:
         rec["other_scaling_row"] = other
-    rec["src_sha"] = tree_stamp()
     if fft:
         rec["roofline"]["traffic_stamp"] = profile_stamp()
     if args.dtype == "f32_fft":

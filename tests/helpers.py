@@ -42,6 +42,31 @@ def golden_array(name, key):
         return z[key]
 
 
+_REF_GRAPHS = {   # kind: (extract() arguments, attribute of tools/extract_dense_hier.py naming the source)
+    "hier": (dict(heads=MG.HIER_HEADS), "REF_HIER"),
+    "dense": (dict(heads=(69,)), "REF_DENSE"),
+    "cnn": (dict(heads=(69,), cls="cnn_model_struct"), "REF_CNN"),
+    "dense_hier": (dict(heads=MG.HIER_HEADS), "REF"),
+}
+
+
+def reference_graph(kind):
+    """(ops, shapes) of the reference's ``kind`` regressor as tools/extract_dense_hier.py reads them
+    from the reference's own build(): one record per op in build order (without the source line) and
+    every tensor's static shape, as committed in tests/golden/<kind>_graph_ops.json.  Where the
+    reference's sources are readable the extraction is run again and must equal the committed file."""
+    with open(os.path.join(GOLDEN, f"{kind}_graph_ops.json")) as f:
+        d = json.load(f)
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import extract_dense_hier as X
+    kw, src = _REF_GRAPHS[kind]
+    if os.access(getattr(X, src), os.R_OK):
+        ops, shapes = X.extract(path=getattr(X, src), **kw)
+        assert [{k: v for k, v in o.items() if k != "line"} for o in ops] == d["ops"], kind
+        assert shapes == d["shapes"], kind
+    return d["ops"], d["shapes"]
+
+
 def rel_inf(a, ref):
     a = np.asarray(a, np.float64)
     ref = np.asarray(ref, np.float64)
@@ -50,3 +75,18 @@ def rel_inf(a, ref):
 
 def pkg():
     return importlib.import_module("monkey-pose_amd")
+
+
+if __name__ == "__main__" and "--regen-graphs" in sys.argv:   # needs the reference's sources
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import extract_dense_hier as X
+    for kind, (kw, src) in _REF_GRAPHS.items():
+        ops, shapes = X.extract(path=getattr(X, src), **kw)
+        ops = [{k: v for k, v in o.items() if k != "line"} for o in ops]
+        path = os.path.join(GOLDEN, f"{kind}_graph_ops.json")
+        with open(path, "w") as f:   # one op per line
+            f.write('{"source": %s,\n"ops": [\n' % json.dumps(
+                f"tools/extract_dense_hier.py extract({kw}) on {os.path.basename(getattr(X, src))}"))
+            f.write(",\n".join(json.dumps(o) for o in ops))
+            f.write('\n],\n"shapes": %s}\n' % json.dumps(shapes))
+        print("wrote", path, len(ops), "ops")

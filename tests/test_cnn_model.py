@@ -1,7 +1,7 @@
 """cnn_model_struct (train_cnn_networks_hgru.py:626-760): the regressor the reference's hGRU driver
 builds for its validation (169), test (291) and real-data evaluation (363) graphs.  Structure
-against the reference's own build (AST extraction, or the committed digest where the reference is
-absent), the float64 oracle against the golden vectors on the CPU, and the GPU graph runtime
+against the reference's own build (AST extraction, committed as data under tests/golden/ and re-run
+where the reference is readable, and the committed digest), the float64 oracle against the golden vectors on the CPU, and the GPU graph runtime
 against both (fp32 gate 1e-4, bf16 gate 5e-3), batch invariance and B = 256."""
 import json
 import os
@@ -9,10 +9,8 @@ import os
 import numpy as np
 import pytest
 
-from helpers import BF16_REL_TOL, FP32_REL_TOL, MG, ROOT, golden_array, golden_meta, pkg, rel_inf
+from helpers import BF16_REL_TOL, FP32_REL_TOL, MG, ROOT, golden_array, golden_meta, pkg, reference_graph, rel_inf
 from oracle import regressors_ref as RR
-
-REF_CNN = "/root/reference/train_cnn_networks_hgru.py"
 
 
 def _inputs():
@@ -40,13 +38,10 @@ def test_cnn_recorded_graph_digest():
     assert pkg()._graph.canonical_digest(rec) == d["sha256"]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CNN), reason="reference sources not present")
 def test_cnn_recorded_graph_is_the_reference_graph():
-    """cnn_model_struct.record() op for op against the reference's own build (AST extraction)."""
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import extract_dense_hier as X
-    ops, _ = X.extract((69,), path=X.REF_CNN, cls="cnn_model_struct")
+    """cnn_model_struct.record() op for op against the reference's own build (AST extraction,
+    committed as tests/golden/cnn_graph_ops.json and re-run where the reference is readable)."""
+    ops, _ = reference_graph("cnn")
     rec = _record().records()
     assert len(rec) == len(ops) == 18
     for a, b in zip(rec, ops):

@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--backend", "gloo", "--batch", "16", "--steps", "2", "--warmup", "1", "--no-extras",
+SMALL = ["--full", "--backend", "gloo", "--batch", "16", "--steps", "2", "--warmup", "1", "--no-extras",
          "--no-cpu-baseline", "--no-parity"]
 
 

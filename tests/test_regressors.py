@@ -3,7 +3,7 @@ regressors: CPU oracle pinned to the golden vectors, GPU path (C ABI) against or
 import numpy as np
 import pytest
 
-from helpers import BF16_REL_TOL, FP32_REL_TOL, MG, golden_array, golden_meta, pkg, rel_inf
+from helpers import BF16_REL_TOL, FP32_REL_TOL, MG, golden_array, golden_meta, pkg, reference_graph, rel_inf
 from oracle import regressors_ref as RR
 
 
@@ -86,17 +86,10 @@ def test_regressors_reject_training():
         pkg().train_hier_networks.hier_model_struct().build(x, 108, 39, 39, 39, 39, 36, batch_norm=["conv_1"])
 
 
-REF_HIER = "/root/reference/train_hier_networks.py"
-
-
-@pytest.mark.skipif(not __import__("os").path.exists(REF_HIER), reason="reference sources not present")
 def test_hier_recorded_graph_is_the_reference_graph():
-    """hier_model_struct.record() op for op against the reference's own build (AST extraction)."""
-    import os
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-    import extract_dense_hier as X
-    ops, _ = X.extract(MG.HIER_HEADS, path=X.REF_HIER)
+    """hier_model_struct.record() op for op against the reference's own build (AST extraction,
+    committed as tests/golden/hier_graph_ops.json and re-run where the reference is readable)."""
+    ops, _ = reference_graph("hier")
     rec = pkg().train_hier_networks.hier_model_struct().record(128, 128, *MG.HIER_HEADS).records()
     assert len(rec) == len(ops) == 91
     for a, b in zip(rec, ops):
@@ -110,17 +103,10 @@ def test_hier_recorded_graph_uses_the_hier_variables():
     assert {v.name: v.shape for v in m._table(g)} == {v.name: v.shape for v in W.hier_vars()}
 
 
-REF_DENSE = "/root/reference/train_dense_networks.py"
-
-
-@pytest.mark.skipif(not __import__("os").path.exists(REF_DENSE), reason="reference sources not present")
 def test_dense_recorded_graph_is_the_reference_graph():
-    """dense_model_struct.record() op for op against the reference's own build (AST extraction)."""
-    import os
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-    import extract_dense_hier as X
-    ops, _ = X.extract((69,), path=X.REF_DENSE)
+    """dense_model_struct.record() op for op against the reference's own build (AST extraction,
+    committed as tests/golden/dense_graph_ops.json and re-run where the reference is readable)."""
+    ops, _ = reference_graph("dense")
     rec = pkg().train_dense_networks.dense_model_struct().record(128, 128, 69).records()
     assert len(rec) == len(ops) == 88
     for a, b in zip(rec, ops):

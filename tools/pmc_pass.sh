@@ -18,6 +18,6 @@ for c in "$@"; do grep -qw "${c%_sum}" "$base/avail.txt" && CTRS="$CTRS $c"; don
 echo "counters:$CTRS (asked: $*)" > "$out/counters.txt"
 [ -n "$CTRS" ] || exit 3
 MP_STREAMS=1 timeout -s KILL 120 rocprofv3 --pmc $CTRS -d "$out/pmc" -o pmc --output-format csv -- \
-  python3 "$R/bench.py" --steps 2 --warmup 1 --no-extras --no-cpu-baseline --no-parity --dtype "$dt" \
+  python3 "$R/bench.py" --full --steps 2 --warmup 1 --no-extras --no-cpu-baseline --no-parity --dtype "$dt" \
   > "$out/pose_$dt.json" 2> "$out/pose_$dt.err"
 echo done > "$out/DONE"

@@ -14,6 +14,6 @@ CTRS=""
 for c in $WANT; do grep -qw "$c" "$out/avail.txt" && CTRS="$CTRS $c"; done
 echo "counters:$CTRS" > "$out/counters.txt"
 MP_STREAMS=1 timeout -s KILL 240 rocprofv3 --pmc $CTRS -d "$out/pmc" -o pmc --output-format csv -- \
-  python3 "$R/bench.py" --steps 2 --warmup 1 --no-extras --no-cpu-baseline --no-parity --dtype "$dt" \
+  python3 "$R/bench.py" --full --steps 2 --warmup 1 --no-extras --no-cpu-baseline --no-parity --dtype "$dt" \
   > "$out/pose_$dt.json" 2> "$out/pose_$dt.err"
 echo done > "$out/DONE"

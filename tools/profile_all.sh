@@ -4,4 +4,5 @@
 set -o pipefail
 bash tools/profile_round.sh "$1" &&
   bash tools/pmc_mfma.sh "gpurun_out/$1/pmc_mfma" f32_fft &&
-  timeout -k 10 420 python bench.py > "gpurun_out/$1/bench_full_fp32.json" 2> "gpurun_out/$1/bench_fp32.err"
+  out=$(dirname "$(ls -t */"$1"/DONE | head -n 1)") &&   # the directory profile_round.sh just wrote
+  timeout -k 10 420 python bench.py --full > "$out/bench_full_fp32.json" 2> "$out/bench_fp32.err"

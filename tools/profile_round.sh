@@ -12,11 +12,11 @@ mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
 for d in f32_fft bf16; do
   MP_STREAMS=1 timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$out/kt_$d" -o kt --output-format csv -- \
-    python3 "$R/bench.py" --steps 5 --warmup 1 --no-extras --no-cpu-baseline --dtype "$d" \
+    python3 "$R/bench.py" --full --steps 5 --warmup 1 --no-extras --no-cpu-baseline --dtype "$d" \
     > "$out/bench_${d}_1stream_under_rocprof.json" 2> "$out/kt_$d.err"
   for c in FETCH_SIZE WRITE_SIZE; do
     MP_STREAMS=1 timeout -s KILL 180 rocprofv3 --pmc "$c" -d "$out/pmc_${d}_$c" -o pmc --output-format csv -- \
-      python3 "$R/bench.py" --steps 2 --warmup 1 --no-extras --no-cpu-baseline --no-parity --dtype "$d" \
+      python3 "$R/bench.py" --full --steps 2 --warmup 1 --no-extras --no-cpu-baseline --no-parity --dtype "$d" \
       > "$out/pmc_${d}_$c.json" 2> "$out/pmc_${d}_$c.err"
   done
 done

@@ -18,7 +18,7 @@ for kv in $PMC; do
   vars=$( [ "$kv" = "-" ] || echo "$kv" | tr ',' ' ')
   for c in FETCH_SIZE WRITE_SIZE; do
     env $vars timeout -s KILL 180 rocprofv3 --pmc "$c" -d "$out/pmc_${kv}_$c" -o pmc --output-format csv -- \
-      python3 "$R/bench.py" --steps 2 --warmup 1 --no-extras --no-cpu-baseline --no-parity \
+      python3 "$R/bench.py" --full --steps 2 --warmup 1 --no-extras --no-cpu-baseline --no-parity \
       > "$out/pmc_${kv}_$c.json" 2> "$out/pmc_${kv}_$c.err" || exit 1
   done
 done

@@ -15,11 +15,11 @@ timeout -k 10 600 python -u -m pytest -x -v --timeout 120 --timeout-method threa
 timeout -k 10 400 python -u -m pytest -x -v --timeout 300 --timeout-method thread tests/test_gpu_bench_ranks.py \
   > "$out/gpu_tests_ranks.log" 2>&1 || exit 1
 export MP_FFT4=0
-timeout -k 10 480 python bench.py > "$out/bench_full_fp32_six_launch.json" 2> "$out/bench_fp32.err" || exit 1
+timeout -k 10 480 python bench.py --full > "$out/bench_full_fp32_six_launch.json" 2> "$out/bench_fp32.err" || exit 1
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -s KILL 180 rocprofv3 --pmc "$c" -d "$out/pmc2s_$c" -o pmc --output-format csv -- \
-    python3 "$R/bench.py" --steps 2 --warmup 1 --no-extras --no-cpu-baseline --no-parity \
+    python3 "$R/bench.py" --full --steps 2 --warmup 1 --no-extras --no-cpu-baseline --no-parity \
     > "$out/pmc2s_$c.json" 2> "$out/pmc2s_$c.err" || exit 1
 done
 echo done > "$out/DONE"

@@ -14,14 +14,14 @@ cp -f "$R/profiles/TREE_STAMP.json" "$out/STAMP_$2.json" 2>/dev/null
 if [ "$2" = A ]; then
   timeout -k 10 780 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread \
     > "$out/gpu_tests.log" 2>&1 || exit 1
-  timeout -k 10 400 python bench.py > "$out/bench_full_fp32.json" 2> "$out/bench_fp32.err" || exit 1
+  timeout -k 10 400 python bench.py --full > "$out/bench_full_fp32.json" 2> "$out/bench_fp32.err" || exit 1
   echo done > "$out/DONE_A"
 else
   bash tools/profile_round.sh "$1" || exit 1
   cd /tmp && export TMPDIR=/tmp
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout -s KILL 180 rocprofv3 --pmc "$c" -d "$out/pmc2s_$c" -o pmc --output-format csv -- \
-      python3 "$R/bench.py" --steps 2 --warmup 1 --no-extras --no-cpu-baseline --no-parity \
+      python3 "$R/bench.py" --full --steps 2 --warmup 1 --no-extras --no-cpu-baseline --no-parity \
       > "$out/pmc2s_$c.json" 2> "$out/pmc2s_$c.err" || exit 1
   done
   cd "$R" && bash tools/pmc_mfma.sh "gpurun_out/$1/mfma" || exit 1

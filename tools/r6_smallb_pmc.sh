@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 for b in "${@:-32 64}"; do
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout -s KILL 180 rocprofv3 --pmc "$c" -d "$out/b${b}_$c" -o pmc --output-format csv -- \
-      python3 "$R/bench.py" --batch "$b" --steps 3 --warmup 1 --no-extras --no-cpu-baseline --no-parity \
+      python3 "$R/bench.py" --full --batch "$b" --steps 3 --warmup 1 --no-extras --no-cpu-baseline --no-parity \
       > "$out/b${b}_$c.json" 2> "$out/b${b}_$c.err" || exit 1
   done
 done

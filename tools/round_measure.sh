@@ -7,5 +7,5 @@ out=gpurun_out/$1
 mkdir -p "$out"
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread > "$out/gpu_tests.log" 2>&1 &&
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1 &&
-  timeout -k 10 420 python bench.py > "$out/bench_full_fp32.json" 2> "$out/bench_fp32.err" &&
-  timeout -k 10 240 python bench.py --dtype bf16 --no-extras > "$out/bench_bf16.json" 2> "$out/bench_bf16.err"
+  timeout -k 10 420 python bench.py --full > "$out/bench_full_fp32.json" 2> "$out/bench_fp32.err" &&
+  timeout -k 10 240 python bench.py --full --dtype bf16 --no-extras > "$out/bench_bf16.json" 2> "$out/bench_bf16.err"
