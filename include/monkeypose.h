@@ -282,6 +282,36 @@ int mp_crop3d_dev_ex(const mp_camera* cam, const float* frames, int64_t n, int64
                      const float* com_norm, const double* com_scale, int flags, int64_t dsize, float* patches,
                      double* Ms, double* coms_out, int32_t* status, void* stream);
 
+/* ---- the detector path on the device (added after 0.3; mp_version() is unchanged) ------------
+ * SURVEY config 5 with MonkeyDetector's own CoM: calculateCoM -> cropArea3D -> pose ->
+ * getAbsoluteCoordinates for a batch without a host step.  All three calls are asynchronous on
+ * `stream`, allocate nothing and synchronise nothing; every pointer except cam is device memory.
+ *
+ * mp_center_of_mass_dev: calculateCoM (monkeydetector.py:66-83) of n float32 frames [n][h][w]; the
+ * detector sees frames * frame_scale (one float32 multiply: 1 for frames in mm, 10000 for frames
+ * normalised by image_max_depth).  coms [n][3] float64 = mp_center_of_mass(MP_DEPTH_F32) of each
+ * frame bit for bit: integer mask sums, and the depth sum in numpy 1.x's float32 pairwise order.
+ * work: scratch of at least mp_center_of_mass_dev_work(n, h, w) bytes (8-byte aligned), reusable
+ * by the next call on the same stream.  n <= 65535, h * w <= 2^30. */
+size_t mp_center_of_mass_dev_work(int64_t n, int64_t h, int64_t w);
+int mp_center_of_mass_dev(const mp_camera* cam, const float* frames, int64_t n, int64_t h, int64_t w,
+                          float frame_scale, double* coms, void* work, size_t work_bytes, void* stream);
+
+/* mp_crop3d_dev_ex around given CoMs: coms [n][3] float64 in device memory (e.g. the output of
+ * mp_center_of_mass_dev) are used as they are, in place of com_norm * com_scale.  flags takes
+ * MP_CROP_DOCOM.  patches, Ms, coms_out and status as mp_crop3d_dev_ex (a CoM of (0,0,0) gives
+ * status 1 and an all-ones patch); coms_out must not alias coms. */
+int mp_crop3d_dev_coms(const mp_camera* cam, const float* frames, int64_t n, int64_t h, int64_t w, float frame_scale,
+                       const double* coms, int flags, int64_t dsize, float* patches, double* Ms, double* coms_out,
+                       int32_t* status, void* stream);
+
+/* getAbsoluteCoordinates (monkeydetector.py:356-360) of a pose output: pose [n][joints * 3] float32
+ * normalised by cube_z / 2 (the regressors' output), coms [n][3] float64 (u, v, d).  Per joint:
+ * xyz = pose * f32(cube_z / 2) + f32(uvdtoxyz(com)) in mm, uvd = xyztouvd(xyz) (a joint with z == 0
+ * maps to (ux, uy, -z)); both [n][joints][3] float32, the bits of the host numpy code. */
+int mp_abs_joints_dev(const mp_camera* cam, const float* pose, int64_t n, int64_t joints, const double* coms,
+                      float* xyz, float* uvd, void* stream);
+
 /* read a model property: "output_shape", "timesteps", "ssf", "finalized", "workspace_bytes",
  * "weight_bytes", "fft_loop" (hGRU contexts: 4 = the four-step FFT loop, 6 = the six-launch FFT
  * loop, 0 = a direct-convolution dtype, no FFT path); graph contexts also "graph_kernels" (kernel launches per forward),

@@ -57,6 +57,21 @@ hipError_t launch_resize_bilinear(const float* x, int N, int H, int W, int C, fl
 
 constexpr int CROP_PIX_PER_BLOCK = 1024;
 
+// The CoM a crop starts from is a template argument, so the attention path's kernels are the code
+// they were.  F64 = false: tr_res[im] * [image_orig_size[0], image_orig_size[1], image_max_depth]
+// (float32 attention output * float64 scale).  F64 = true (mp_crop3d_dev_coms, the detector path):
+// com_norm points at [n][3] float64 CoMs, taken as they are.
+#define MP_CROP_COM_IN(com)                                                                     \
+  double com[3] = {(double)com_norm[3 * f] * cs0, (double)com_norm[3 * f + 1] * cs1,            \
+                   (double)com_norm[3 * f + 2] * cs2};                                          \
+  if constexpr (F64) {                                                                          \
+    const double* c64 = reinterpret_cast<const double*>(com_norm);                              \
+    com[0] = c64[3 * f];                                                                        \
+    com[1] = c64[3 * f + 1];                                                                    \
+    com[2] = c64[3 * f + 2];                                                                    \
+  }
+
+template <bool F64>
 __global__ __launch_bounds__(256) void crop3d_kernel(mp_camera cam, const float* __restrict__ frames, int H, int W,
                                                      float frame_scale, const float* __restrict__ com_norm,
                                                      double cs0, double cs1, double cs2, int dsz,
@@ -72,8 +87,7 @@ __global__ __launch_bounds__(256) void crop3d_kernel(mp_camera cam, const float*
     // (the first crop's failure, or the refined crop's geometry status).  In the refined form every
     // block only READS coms_out / status (crop_refine_kernel, the previous launch, wrote them), so
     // no block's read races another block's write; unrefined, the other blocks never read them.
-    double com[3] = {(double)com_norm[3 * f] * cs0, (double)com_norm[3 * f + 1] * cs1,
-                     (double)com_norm[3 * f + 2] * cs2};
+    MP_CROP_COM_IN(com)
     if (refined) {
       com[0] = coms_out[3 * f];
       com[1] = coms_out[3 * f + 1];
@@ -208,6 +222,7 @@ __device__ float pairwise_dc(const mpgeom::CropGeom& g, const float* fr, int W, 
   return vals[0];
 }
 
+template <bool F64>
 __global__ __launch_bounds__(REF_T) void crop_refine_kernel(mp_camera cam, const float* __restrict__ frames, int H,
                                                             int W, float frame_scale, const float* __restrict__ com_norm,
                                                             double cs0, double cs1, double cs2, int dsz,
@@ -221,8 +236,7 @@ __global__ __launch_bounds__(REF_T) void crop_refine_kernel(mp_camera cam, const
   const int f = blockIdx.x, t = threadIdx.x;
   const float* fr = frames + (size_t)f * H * W;
   if (t == 0) {
-    double com[3] = {(double)com_norm[3 * f] * cs0, (double)com_norm[3 * f + 1] * cs1,
-                     (double)com_norm[3 * f + 2] * cs2};
+    MP_CROP_COM_IN(com)
     st = mpgeom::crop_geometry(cam, com, H, W, dsz, &g);
     const int64_t n = st == mpgeom::CROP_OK ? g.rows * g.cols : 0;
     int d = 0;
@@ -302,16 +316,33 @@ __global__ __launch_bounds__(REF_T) void crop_refine_kernel(mp_camera cam, const
   }
 }
 
+template <bool F64>
+static hipError_t launch_crop3d_t(const mp_camera& cam, const float* frames, int N, int H, int W, float frame_scale,
+                                  const float* com_norm, const double com_scale[3], int dsz, float* patches,
+                                  double* Ms, double* coms_out, int32_t* status, hipStream_t st, bool docom) {
+  const int nb = (dsz * dsz + CROP_PIX_PER_BLOCK - 1) / CROP_PIX_PER_BLOCK;
+  if (docom)
+    hipLaunchKernelGGL(crop_refine_kernel<F64>, dim3(N), dim3(REF_T), 0, st, cam, frames, H, W, frame_scale,
+                       com_norm, com_scale[0], com_scale[1], com_scale[2], dsz, coms_out, status);
+  hipLaunchKernelGGL(crop3d_kernel<F64>, dim3(nb, N), dim3(256), 0, st, cam, frames, H, W, frame_scale, com_norm,
+                     com_scale[0], com_scale[1], com_scale[2], dsz, patches, Ms, coms_out, status, docom ? 1 : 0);
+  return hipGetLastError();
+}
+
 hipError_t launch_crop3d(const mp_camera& cam, const float* frames, int N, int H, int W, float frame_scale,
                          const float* com_norm, const double com_scale[3], int dsz, float* patches, double* Ms,
                          double* coms_out, int32_t* status, hipStream_t st, bool docom) {
-  const int nb = (dsz * dsz + CROP_PIX_PER_BLOCK - 1) / CROP_PIX_PER_BLOCK;
-  if (docom)
-    hipLaunchKernelGGL(crop_refine_kernel, dim3(N), dim3(REF_T), 0, st, cam, frames, H, W, frame_scale, com_norm,
-                       com_scale[0], com_scale[1], com_scale[2], dsz, coms_out, status);
-  hipLaunchKernelGGL(crop3d_kernel, dim3(nb, N), dim3(256), 0, st, cam, frames, H, W, frame_scale, com_norm,
-                     com_scale[0], com_scale[1], com_scale[2], dsz, patches, Ms, coms_out, status, docom ? 1 : 0);
-  return hipGetLastError();
+  return launch_crop3d_t<false>(cam, frames, N, H, W, frame_scale, com_norm, com_scale, dsz, patches, Ms, coms_out,
+                                status, st, docom);
+}
+
+// the same crop around given float64 CoMs [N][3] (device memory, not aliasing coms_out)
+hipError_t launch_crop3d_coms(const mp_camera& cam, const float* frames, int N, int H, int W, float frame_scale,
+                              const double* coms, int dsz, float* patches, double* Ms, double* coms_out,
+                              int32_t* status, hipStream_t st, bool docom) {
+  const double unit[3] = {1.0, 1.0, 1.0};   // unused by the float64 form
+  return launch_crop3d_t<true>(cam, frames, N, H, W, frame_scale, reinterpret_cast<const float*>(coms), unit, dsz,
+                               patches, Ms, coms_out, status, st, docom);
 }
 
 // hidden_init 'random' (hgru_module.py:879-887) drawn on the device: element i of O0 is

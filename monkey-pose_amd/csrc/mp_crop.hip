@@ -410,4 +410,61 @@ int mp_crop3d_dev_ex(const mp_camera* cam, const float* frames, int64_t n, int64
   });
 }
 
+// ---- the detector path on the device (k_detect.hip) --------------------------------------------
+static void check_dev_frames(const char* who, int64_t n, int64_t h, int64_t w) {
+  if (n <= 0 || n > 65535 || h <= 0 || w <= 0 || h * w > ((int64_t)1 << 30))
+    fail(MP_ERR_SHAPE, std::string(who) + ": bad shape");
+}
+
+size_t mp_center_of_mass_dev_work(int64_t n, int64_t h, int64_t w) {
+  if (n <= 0 || n > 65535 || h <= 0 || w <= 0 || h * w > ((int64_t)1 << 30)) return 0;
+  return mp::com_work_bytes(n, h * w);
+}
+
+int mp_center_of_mass_dev(const mp_camera* cam, const float* frames, int64_t n, int64_t h, int64_t w,
+                          float frame_scale, double* coms, void* work, size_t work_bytes, void* stream) {
+  return guard([&] {
+    check_cam(cam);
+    if (!frames || !coms || !work) fail(MP_ERR_ARG, "mp_center_of_mass_dev: null pointer");
+    check_dev_frames("mp_center_of_mass_dev", n, h, w);
+    if (work_bytes < mp::com_work_bytes(n, h * w))
+      fail(MP_ERR_ARG, "mp_center_of_mass_dev: work buffer smaller than mp_center_of_mass_dev_work()");
+    if (reinterpret_cast<uintptr_t>(work) & 7) fail(MP_ERR_ARG, "mp_center_of_mass_dev: work must be 8-byte aligned");
+    const Thresh<float> th(*cam);   // the host center_of_mass's float32 bounds
+    hip_check(mp::launch_center_of_mass(frames, (int)n, (int)h, (int)w, frame_scale, th.lo, th.hi, coms, work,
+                                        static_cast<hipStream_t>(stream)),
+              "center_of_mass");
+  });
+}
+
+int mp_crop3d_dev_coms(const mp_camera* cam, const float* frames, int64_t n, int64_t h, int64_t w, float frame_scale,
+                       const double* coms, int flags, int64_t dsize, float* patches, double* Ms, double* coms_out,
+                       int32_t* status, void* stream) {
+  return guard([&] {
+    check_cam(cam);
+    if (flags & ~MP_CROP_DOCOM) fail(MP_ERR_ARG, "mp_crop3d_dev_coms: unknown flags");
+    if (!frames || !coms || !patches || !Ms || !coms_out || !status)
+      fail(MP_ERR_ARG, "mp_crop3d_dev_coms: null pointer");
+    if (coms == coms_out) fail(MP_ERR_ARG, "mp_crop3d_dev_coms: coms and coms_out must not alias");
+    check_dev_frames("mp_crop3d_dev_coms", n, h, w);
+    if (dsize <= 0 || dsize > 4096) fail(MP_ERR_SHAPE, "mp_crop3d_dev_coms: bad shape");
+    if (!(cam->max_depth != 0.0)) fail(MP_ERR_ARG, "camera max_depth must be non-zero");
+    hip_check(mp::launch_crop3d_coms(*cam, frames, (int)n, (int)h, (int)w, frame_scale, coms, (int)dsize, patches,
+                                     Ms, coms_out, status, static_cast<hipStream_t>(stream),
+                                     (flags & MP_CROP_DOCOM) != 0),
+              "crop3d_coms");
+  });
+}
+
+int mp_abs_joints_dev(const mp_camera* cam, const float* pose, int64_t n, int64_t joints, const double* coms,
+                      float* xyz, float* uvd, void* stream) {
+  return guard([&] {
+    check_cam(cam);
+    if (!pose || !coms || !xyz || !uvd) fail(MP_ERR_ARG, "mp_abs_joints_dev: null pointer");
+    if (n <= 0 || joints <= 0 || joints > 65535 || n > ((int64_t)1 << 24)) fail(MP_ERR_SHAPE, "mp_abs_joints_dev: bad shape");
+    hip_check(mp::launch_abs_joints(*cam, pose, n, (int)joints, coms, xyz, uvd, static_cast<hipStream_t>(stream)),
+              "abs_joints");
+  });
+}
+
 }  // extern "C"

@@ -158,6 +158,15 @@ hipError_t launch_hidden_uniform(float* out, int64_t n, uint64_t seed, double li
 hipError_t launch_crop3d(const mp_camera& cam, const float* frames, int N, int H, int W, float frame_scale,
                          const float* com_norm, const double com_scale[3], int dsz, float* patches, double* Ms,
                          double* coms_out, int32_t* status, hipStream_t st, bool docom = false);
+hipError_t launch_crop3d_coms(const mp_camera& cam, const float* frames, int N, int H, int W, float frame_scale,
+                              const double* coms, int dsz, float* patches, double* Ms, double* coms_out,
+                              int32_t* status, hipStream_t st, bool docom = false);
+// k_detect.hip (the detector path: full-frame calculateCoM, getAbsoluteCoordinates)
+size_t com_work_bytes(int64_t n, int64_t hw);
+hipError_t launch_center_of_mass(const float* frames, int N, int H, int W, float frame_scale, float lo_t,
+                                 float hi_t, double* coms, void* work, hipStream_t st);
+hipError_t launch_abs_joints(const mp_camera& cam, const float* pose, int64_t n, int joints, const double* coms,
+                             float* xyz, float* uvd, hipStream_t st);
 hipError_t launch_fc_reduce(const float* part, int S, int M, int N, const float* bias, int relu,
                             const float* aff_s, const float* aff_t, float* out, int ldo, hipStream_t st);
 

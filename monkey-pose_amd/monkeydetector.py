@@ -43,6 +43,16 @@ _CROP_SIGS = {
                                         ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "mp_center_of_mass_dev_work": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    "mp_center_of_mass_dev": (ctypes.c_int, [ctypes.POINTER(_Camera), ctypes.c_void_p, ctypes.c_int64,
+                                             ctypes.c_int64, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "mp_crop3d_dev_coms": (ctypes.c_int, [ctypes.POINTER(_Camera), ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                          ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_int,
+                                          ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p]),
+    "mp_abs_joints_dev": (ctypes.c_int, [ctypes.POINTER(_Camera), ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 _CROP_MSG = {1: "CoM depth is zero or not finite (no valid pixel in range?)", 2: "empty crop",
@@ -196,6 +206,141 @@ class MonkeyDetector(object):
                 code = int(status[bad[0]].item())
                 raise _lib.MonkeyPoseError(-1, f"frame {bad[0]}: cropArea3D: {_CROP_MSG.get(code, code)}")
         return patches, Ms, coms
+
+    # ------------------------------------------------------------------ detector path on the device
+    @staticmethod
+    def _dev_frames(frames, coms=None):
+        """``frames`` ([n, h, w] or [n, h, w, 1]) as a contiguous fp32 CUDA [n, h, w] tensor; the
+        shapes (also of ``coms`` [n, 3], when given) are checked first, then the device, both before
+        any GPU call."""
+        import torch
+        if not isinstance(frames, torch.Tensor):
+            raise TypeError("frames must be a CUDA (ROCm) tensor")
+        if frames.dim() == 4:
+            if frames.shape[-1] != 1:
+                raise ValueError("frames must be single-channel")
+            frames = frames[..., 0]
+        if frames.dim() != 3 or 0 in frames.shape:
+            raise ValueError(f"frames must be [n, h, w], got {tuple(frames.shape)}")
+        if isinstance(coms, torch.Tensor) and tuple(coms.shape) != (frames.shape[0], 3):
+            raise ValueError(f"coms must be [{frames.shape[0]}, 3], got {tuple(coms.shape)}")
+        if not frames.is_cuda:
+            raise TypeError("frames must be a CUDA (ROCm) tensor")
+        return frames.detach().float().contiguous()
+
+    @staticmethod
+    def _dev_coms(coms, n):
+        import torch
+        if not isinstance(coms, torch.Tensor):
+            raise TypeError("coms must be a CUDA (ROCm) tensor")
+        if tuple(coms.shape) != (n, 3):
+            raise ValueError(f"coms must be [{n}, 3], got {tuple(coms.shape)}")
+        if not coms.is_cuda:
+            raise TypeError("coms must be a CUDA (ROCm) tensor")
+        return coms.detach().double().contiguous()
+
+    def _detect_buffers(self, n, h, w, dsize, dev):
+        """output and scratch tensors of one detector batch (``DetectorPosePipeline`` keeps them)"""
+        import torch
+        nbytes = int(_lib_crop().mp_center_of_mass_dev_work(n, h, w))
+        return dict(
+            work=torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev), work_bytes=nbytes,
+            coms0=torch.empty((n, 3), dtype=torch.float64, device=dev),
+            patches=torch.empty((n, dsize, dsize, 1), dtype=torch.float32, device=dev),
+            Ms=torch.empty((n, 3, 3), dtype=torch.float64, device=dev),
+            coms=torch.empty((n, 3), dtype=torch.float64, device=dev),
+            status=torch.empty((n,), dtype=torch.int32, device=dev))
+
+    def _com_into(self, fr, frame_scale, coms, work, work_bytes, st):
+        n, h, w = fr.shape
+        cam = self._cam()
+        _lib.check(_lib_crop().mp_center_of_mass_dev(ctypes.byref(cam), ctypes.c_void_p(fr.data_ptr()), n, h, w,
+                                                     float(frame_scale), ctypes.c_void_p(coms.data_ptr()),
+                                                     ctypes.c_void_p(work.data_ptr()), work_bytes,
+                                                     ctypes.c_void_p(st)))
+
+    def _crop_coms_into(self, fr, frame_scale, coms_in, dsize, docom, b, st):
+        n, h, w = fr.shape
+        cam = self._cam()
+        _lib.check(_lib_crop().mp_crop3d_dev_coms(ctypes.byref(cam), ctypes.c_void_p(fr.data_ptr()), n, h, w,
+                                                  float(frame_scale), ctypes.c_void_p(coms_in.data_ptr()),
+                                                  1 if docom else 0, int(dsize),
+                                                  ctypes.c_void_p(b["patches"].data_ptr()),
+                                                  ctypes.c_void_p(b["Ms"].data_ptr()),
+                                                  ctypes.c_void_p(b["coms"].data_ptr()),
+                                                  ctypes.c_void_p(b["status"].data_ptr()), ctypes.c_void_p(st)))
+
+    def _check_status(self, status):
+        import torch
+        self.last_status = status
+        bad = torch.nonzero(status).flatten().tolist()   # the one sync of a checked call
+        if bad:
+            code = int(status[bad[0]].item())
+            raise _lib.MonkeyPoseError(-1, f"frame {bad[0]}: cropArea3D: {_CROP_MSG.get(code, code)}")
+
+    def calculateCoM_device(self, frames, frame_scale=1.0, stream=None):
+        """``calculateCoM`` (monkeydetector.py:66-83) of every frame of a CUDA batch [n, h, w] (or
+        [n, h, w, 1]) fp32 in one asynchronous call (``mp_center_of_mass_dev``): a CUDA [n, 3] float64
+        tensor, each row the bits of ``calculateCoM(frame * frame_scale)`` (``frame_scale`` 1 for
+        frames in mm, 10000 for normalised frames)."""
+        fr = self._dev_frames(frames)
+        import torch
+        n, h, w = fr.shape
+        nbytes = int(_lib_crop().mp_center_of_mass_dev_work(n, h, w))
+        work = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=fr.device)
+        coms = torch.empty((n, 3), dtype=torch.float64, device=fr.device)
+        st = _lib.current_stream(fr.device) if stream is None else stream
+        self._com_into(fr, frame_scale, coms, work, nbytes, st)
+        return coms
+
+    def detect_crop_device(self, frames, coms=None, frame_scale=1.0, dsize=128, docom=False, check=True,
+                           stream=None, _buffers=None):
+        """``crop_batch`` on the GPU: ``cropArea3D(frame * frame_scale, com)`` / maxDepth per frame
+        with ``coms`` a CUDA [n, 3] float64 tensor taken as it is (``mp_crop3d_dev_coms``), or
+        ``None`` for the detector's own ``calculateCoM`` on the device first.  Returns (patches CUDA
+        [n, dsize, dsize, 1], Ms CUDA [n, 3, 3] f64, coms CUDA [n, 3] f64) with the outputs, status
+        codes and ``check`` semantics of ``crop_batch_device``."""
+        fr = self._dev_frames(frames, coms)
+        n, h, w = fr.shape
+        cin = None if coms is None else self._dev_coms(coms, n)
+        b = _buffers if _buffers is not None else self._detect_buffers(n, h, w, int(dsize), fr.device)
+        st = _lib.current_stream(fr.device) if stream is None else stream
+        if cin is None:
+            cin = b["coms0"]
+            self._com_into(fr, frame_scale, cin, b["work"], b["work_bytes"], st)
+        self._crop_coms_into(fr, frame_scale, cin, dsize, docom, b, st)
+        self.last_status = b["status"]
+        if check:
+            self._check_status(b["status"])
+        return b["patches"], b["Ms"], b["coms"]
+
+    def getAbsoluteCoordinates_device(self, pose, coms, num_joints=23, stream=None, out=None):
+        """``getAbsoluteCoordinates`` (monkeydetector.py:356-360) for a batch on the GPU
+        (``mp_abs_joints_dev``): ``pose`` CUDA [n, num_joints * 3] fp32 normalised by cube_z / 2 (a
+        regressor's output), ``coms`` CUDA [n, 3] f64 -> (xyz mm, uvd), CUDA fp32 [n, num_joints, 3]."""
+        import torch
+        J = int(num_joints)
+        if not isinstance(pose, torch.Tensor):
+            raise TypeError("pose must be a CUDA (ROCm) tensor")
+        if pose.dim() != 2 or pose.shape[0] == 0 or pose.shape[1] != 3 * J:
+            raise ValueError(f"pose must be [n, {3 * J}], got {tuple(pose.shape)}")
+        n = pose.shape[0]
+        if isinstance(coms, torch.Tensor) and tuple(coms.shape) != (n, 3):
+            raise ValueError(f"coms must be [{n}, 3], got {tuple(coms.shape)}")
+        if not pose.is_cuda:
+            raise TypeError("pose must be a CUDA (ROCm) tensor")
+        c = self._dev_coms(coms, n)
+        p = pose.detach().float().contiguous()
+        if out is None:
+            out = (torch.empty((n, J, 3), dtype=torch.float32, device=p.device),
+                   torch.empty((n, J, 3), dtype=torch.float32, device=p.device))
+        xyz, uvd = out
+        st = _lib.current_stream(p.device) if stream is None else stream
+        cam = self._cam()
+        _lib.check(_lib_crop().mp_abs_joints_dev(ctypes.byref(cam), ctypes.c_void_p(p.data_ptr()), n, J,
+                                                 ctypes.c_void_p(c.data_ptr()), ctypes.c_void_p(xyz.data_ptr()),
+                                                 ctypes.c_void_p(uvd.data_ptr()), ctypes.c_void_p(st)))
+        return xyz, uvd
 
     # ------------------------------------------------------------------ geometry (host numpy)
     def comToBounds(self, com, size):

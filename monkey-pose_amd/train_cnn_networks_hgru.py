@@ -161,6 +161,48 @@ class FramePosePipeline:
         return out, coms, Ms
 
 
+class DetectorPosePipeline:
+    """SURVEY config 5 for a batch, device-resident: ``MonkeyDetector``'s own ``calculateCoM`` of
+    every frame (``mp_center_of_mass_dev``) -> device crop around those float64 CoMs
+    (``mp_crop3d_dev_coms``) -> the pose forward -> absolute joints (``mp_abs_joints_dev``), all on
+    the current stream with no host round trip; the only sync is the status read when
+    ``check_crops`` is set.  The batch counterpart of ``StreamPosePipeline`` (same bits per frame).
+
+    ``pose_model``: a pose regressor with ``build(patches, num_classes, h2_init=)`` /
+    ``forward(patches, h2_init=)`` (``hgru_pose.model``).  ``frame_scale``: 1 for frames in mm,
+    10000 for frames normalised by the maximum depth.  ``run(frames, h2_init=None)`` with ``frames``
+    CUDA [n, h, w] or [n, h, w, 1] fp32 -> (xyz [n, J, 3] mm, uvd [n, J, 3], coms [n, 3] f64,
+    Ms [n, 3, 3] f64), CUDA tensors reused by the next call of the same batch shape."""
+
+    def __init__(self, pose_model, md, dsize: int = 128, num_joints: int = 23, docom: bool = False,
+                 frame_scale: float = 1.0, check_crops: bool = True):
+        self.pose, self.md = pose_model, md
+        self.dsize, self.num_joints = int(dsize), int(num_joints)
+        self.docom, self.frame_scale, self.check_crops = bool(docom), float(frame_scale), bool(check_crops)
+        self._key, self._buf, self._out = None, None, None
+
+    def run(self, frames, h2_init=None):
+        import torch
+        md = self.md
+        fr = md._dev_frames(frames)          # shape, then device: raises before any GPU call
+        n, h, w = fr.shape
+        key = (n, h, w, fr.device)
+        if key != self._key:
+            self._buf = md._detect_buffers(n, h, w, self.dsize, fr.device)
+            self._out = tuple(torch.empty((n, self.num_joints, 3), dtype=torch.float32, device=fr.device)
+                              for _ in range(2))
+            self._key = key
+        patches, Ms, coms = md.detect_crop_device(fr, None, frame_scale=self.frame_scale, dsize=self.dsize,
+                                                  docom=self.docom, check=self.check_crops, _buffers=self._buf)
+        nc = self.num_joints * 3
+        if getattr(self.pose, "_ctx", None) is None:
+            out = self.pose.build(patches, nc, h2_init=h2_init)
+        else:
+            out = self.pose.forward(patches, h2_init=h2_init)
+        xyz, uvd = md.getAbsoluteCoordinates_device(out, coms, self.num_joints, out=self._out)
+        return xyz, uvd, coms, Ms
+
+
 class StreamPosePipeline:
     """SURVEY config 5, one depth frame per call: the host CoM crop of ``MonkeyDetector`` (native
     ``mp_crop3d_batch``) -> the hGRU pose forward at batch 1 -> absolute joints
