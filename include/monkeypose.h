@@ -312,6 +312,61 @@ int mp_crop3d_dev_coms(const mp_camera* cam, const float* frames, int64_t n, int
 int mp_abs_joints_dev(const mp_camera* cam, const float* pose, int64_t n, int64_t joints, const double* coms,
                       float* xyz, float* uvd, void* stream);
 
+/* ---- the validation pass on the device (added after 0.3; mp_version() is unchanged) -----------
+ * Labels, joint errors and metrics of a labelled batch (train_cnn_networks_hgru.py:160-173, 229-237;
+ * pose_evaluation.py) without a host step.  Every call that takes `stream` is asynchronous on it,
+ * allocates nothing and synchronises nothing; every pointer except cam and thresholds is device
+ * memory.  joints <= 128 (numpy's pairwise sum is one leaf up to there), n <= 65535.
+ *
+ * mp_rel_labels_dev: the label half of prepare_data (train_cnn_networks_hgru.py:52-56): labels
+ * [n][joints][3] float32 absolute xyz in mm, coms [n][3] float64 (the crop's coms_out) ->
+ * rel [n][joints * 3] float32 = clip((label - f32(uvdtoxyz(com))) / f32(cube_z / 2), -1, 1); the
+ * subtraction and division are float32, a NaN label stays NaN (numpy.clip).  f32(uvdtoxyz(com)) has
+ * the bits mp_abs_joints_dev uses. */
+int mp_rel_labels_dev(const mp_camera* cam, const float* labels, int64_t n, int64_t joints, const double* coms,
+                      float* rel, void* stream);
+
+/* tfMonkeyDetector.calculateCoMfrom3DJoints (tf_monkeydetector.py:66-71) and the driver's
+ * normalisation (train_cnn_networks_hgru.py:166): labels [n][joints][3] float32 -> com [n][3]
+ * float32.  The mean over the joints is a sequential float32 sum in joint order divided by
+ * f32(joints); then xyztouvd in float32 with no z == 0 guard (inf / NaN propagate):
+ * u = f32(ux) - (x / z) * f32(fx), v = f32(uy) + (y / z) * f32(fy), d = -z; then u, v, d are divided
+ * by f32(scale_u), f32(scale_v), f32(scale_d) (pass 1, 1, 1 for the plain uvd). */
+int mp_com_from_joints_dev(const mp_camera* cam, const float* labels, int64_t n, int64_t joints, double scale_u,
+                           double scale_v, double scale_d, float* com, void* stream);
+
+/* A streaming evaluator: a state in device memory that mp_eval_accumulate_dev updates per batch.
+ *   state   mp_eval_state_bytes(joints, T) bytes, 8-byte aligned; T <= 1024 thresholds (0 if
+ *           joints or T is out of range)
+ *   mp_eval_reset_dev  zeroes the state and stores thresholds [T] float32, a HOST array read at
+ *           the call
+ *   mp_eval_accumulate_dev  labels, results [n][joints][3] float32, both multiplied by the float32
+ *           `scale` first (1 for mm, f32(cube_z / 2) for normalised values).  Per joint
+ *           d = sqrtf(((dx * dx) + (dy * dy)) + dz * dz); per frame, NaN-aware as numpy.nanmean /
+ *           nanmax over the joints in numpy's float32 order: frame_mean, frame_max (NaN when every
+ *           joint is NaN).  The state gains: frames, frames whose mean is not NaN, the float64 sum
+ *           of frame_mean, the largest distance, per joint the float64 sum of distances and the
+ *           non-NaN count, and per threshold the frames with frame_max <= t and with
+ *           frame_mean <= t.  No floating-point atomics: the float64 sums run in frame order, so a
+ *           sequence of calls leaves the same bytes whenever it is repeated, and the same sums
+ *           however the frames are cut into batches.
+ *           work: scratch of at least mp_eval_work_bytes(n, joints) bytes, 8-byte aligned.
+ *           dist [n][joints], frame_mean [n], frame_max [n]: optional float32 outputs (NULL allowed).
+ *           joints and T must be those of the reset; a state that was reset for others is left as
+ *           it is and its summary is all NaN.
+ *   mp_eval_summary_dev  out [mp_eval_summary_len(joints, T)] float64: frames, valid_frames,
+ *           mean_error, max_error, joint_mean[joints], within_max[T], within_mean[T]; the two
+ *           within arrays in percent of all frames (count / frames * 100).  With joints = 1 the
+ *           mean_error is calc_com_error (train_cnn_networks_hgru.py:36-39). */
+size_t mp_eval_state_bytes(int64_t joints, int64_t T);
+size_t mp_eval_work_bytes(int64_t n, int64_t joints);
+int mp_eval_reset_dev(void* state, int64_t joints, int64_t T, const float* thresholds, void* stream);
+int mp_eval_accumulate_dev(void* state, const float* labels, const float* results, int64_t n, int64_t joints,
+                           int64_t T, float scale, void* work, size_t work_bytes, float* dist, float* frame_mean,
+                           float* frame_max, void* stream);
+int64_t mp_eval_summary_len(int64_t joints, int64_t T);
+int mp_eval_summary_dev(const void* state, int64_t joints, int64_t T, double* out, void* stream);
+
 /* read a model property: "output_shape", "timesteps", "ssf", "finalized", "workspace_bytes",
  * "weight_bytes", "fft_loop" (hGRU contexts: 4 = the four-step FFT loop, 6 = the six-launch FFT
  * loop, 0 = a direct-convolution dtype, no FFT path); graph contexts also "graph_kernels" (kernel launches per forward),

@@ -12,7 +12,8 @@ The directory name carries a hyphen, so import it with ``importlib.import_module
 * ``train_cnn_networks_hgru`` -- ``attn_model_struct`` (the attention CoM regressor),
   ``prepare_data_test`` (device batch crop) and ``FramePosePipeline`` (frame -> CoM -> crop -> pose)
 * ``monkeydetector`` -- ``MonkeyDetector`` / ``tfMonkeyDetector``: CoM, crop (native), joint transforms
-* ``pose_evaluation`` -- the host metrics (``getMeanError_np`` ...)
+* ``pose_evaluation`` -- the pose metrics (``getMeanError_np`` ...) on numpy arrays and on CUDA tensors,
+  ``PoseEvaluator`` (a streaming evaluator in device memory)
 * ``weights``     -- TF variable-name tables and deterministic synthetic initialisers
 * ``tf_checkpoint`` -- TF1 V2 checkpoint reader / writer (no TensorFlow needed)
 * ``data_loader`` -- TFRecord ingestion (``inputs`` / ``read_and_decode``, ``create_tf_record``)

@@ -227,10 +227,8 @@ __global__ __launch_bounds__(256) void abs_joints_kernel(mp_camera cam, const fl
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   const int64_t f = i / joints;
-  const double u0 = coms[3 * f], u1 = coms[3 * f + 1], u2 = coms[3 * f + 2];
-  const float cx = (float)((cam.ux - u0) * u2 / (-cam.fx));
-  const float cy = (float)((u1 - cam.uy) * u2 / (-cam.fy));
-  const float cz = (float)(-u2);
+  float cx, cy, cz;
+  com_uvd_to_xyz(cam, coms + 3 * f, &cx, &cy, &cz);
   const float rx = pose[3 * i] * half_z, ry = pose[3 * i + 1] * half_z, rz = pose[3 * i + 2] * half_z;
   const float x = rx + cx, y = ry + cy, z = rz + cz;
   xyz[3 * i] = x;

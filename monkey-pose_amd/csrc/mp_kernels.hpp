@@ -169,5 +169,28 @@ hipError_t launch_abs_joints(const mp_camera& cam, const float* pose, int64_t n,
                              float* xyz, float* uvd, hipStream_t st);
 hipError_t launch_fc_reduce(const float* part, int S, int M, int N, const float* bias, int relu,
                             const float* aff_s, const float* aff_t, float* out, int ldo, hipStream_t st);
+// f32(uvdtoxyz(com)) of a crop's float64 CoM (u, v, d), monkeydetector.py:114-131: float64 operations,
+// one rounding to float32 each.  Shared by abs_joints_kernel (k_detect.hip) and rel_labels_kernel
+// (k_eval.hip), which must agree bit for bit.
+__device__ __forceinline__ void com_uvd_to_xyz(const mp_camera& cam, const double* __restrict__ com, float* cx,
+                                               float* cy, float* cz) {
+#pragma clang fp contract(off)
+  const double u0 = com[0], u1 = com[1], u2 = com[2];
+  *cx = (float)((cam.ux - u0) * u2 / (-cam.fx));
+  *cy = (float)((u1 - cam.uy) * u2 / (-cam.fy));
+  *cz = (float)(-u2);
+}
+// k_eval.hip (the validation pass: label half of prepare_data, calculateCoMfrom3DJoints, joint
+// errors and the streaming evaluator state)
+hipError_t launch_rel_labels(const mp_camera& cam, const float* labels, int64_t n, int joints, const double* coms,
+                             float* rel, hipStream_t st);
+hipError_t launch_com_from_joints(const mp_camera& cam, const float* labels, int64_t n, int joints, float s0,
+                                  float s1, float s2, float* com, hipStream_t st);
+size_t eval_state_bytes(int J, int T);
+size_t eval_work_bytes(int64_t n, int J);
+hipError_t launch_eval_reset(void* state, int J, int T, const float* thresholds_host, hipStream_t st);
+hipError_t launch_eval_accumulate(void* state, const float* labels, const float* results, int64_t n, int J, int T,
+                                  float scale, float* dist, float* frame_mean, float* frame_max, hipStream_t st);
+hipError_t launch_eval_summary(const void* state, int J, int T, double* out, hipStream_t st);
 
 }  // namespace mp

@@ -53,7 +53,28 @@ _CROP_SIGS = {
                                           ctypes.c_void_p, ctypes.c_void_p]),
     "mp_abs_joints_dev": (ctypes.c_int, [ctypes.POINTER(_Camera), ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    # the validation pass on the device (k_eval.hip)
+    "mp_rel_labels_dev": (ctypes.c_int, [ctypes.POINTER(_Camera), ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "mp_com_from_joints_dev": (ctypes.c_int, [ctypes.POINTER(_Camera), ctypes.c_void_p, ctypes.c_int64,
+                                              ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                              ctypes.c_void_p, ctypes.c_void_p]),
+    "mp_eval_state_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64]),
+    "mp_eval_work_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64]),
+    "mp_eval_reset_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                                         ctypes.c_void_p]),
+    "mp_eval_accumulate_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                              ctypes.c_int64, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p,
+                                              ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p]),
+    "mp_eval_summary_len": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64]),
+    "mp_eval_summary_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                                           ctypes.c_void_p]),
 }
+
+MAX_EVAL_JOINTS = 128       # eval_plan.hpp MAX_JOINTS: numpy's pairwise sum is one leaf up to there
+MAX_EVAL_THRESHOLDS = 1024
+MAX_DEV_FRAMES = 65535
 
 _CROP_MSG = {1: "CoM depth is zero or not finite (no valid pixel in range?)", 2: "empty crop",
              3: "degenerate bounds", 4: "resize target is empty"}
@@ -341,6 +362,104 @@ class MonkeyDetector(object):
                                                  ctypes.c_void_p(c.data_ptr()), ctypes.c_void_p(xyz.data_ptr()),
                                                  ctypes.c_void_p(uvd.data_ptr()), ctypes.c_void_p(st)))
         return xyz, uvd
+
+    # ------------------------------------------------------------------ labels (validation pass)
+    @staticmethod
+    def _dev_labels(labels, name="labels", num_joints=None, shape_only=False):
+        """``labels`` [n, J, 3] (or [n, 3J] with ``num_joints``) as a contiguous fp32 CUDA [n, J, 3]
+        tensor; the shape is checked first, then the device, both before any GPU call
+        (``shape_only``: the reshaped tensor after the shape checks alone)."""
+        import torch
+        if not isinstance(labels, torch.Tensor):
+            raise TypeError(f"{name} must be a CUDA (ROCm) tensor")
+        if labels.dim() == 2 and num_joints is not None and labels.shape[1] == 3 * int(num_joints):
+            labels = labels.reshape(labels.shape[0], int(num_joints), 3)
+        if labels.dim() != 3 or labels.shape[2] != 3 or 0 in labels.shape:
+            raise ValueError(f"{name} must be [n, joints, 3], got {tuple(labels.shape)}")
+        if labels.shape[1] > MAX_EVAL_JOINTS:
+            raise ValueError(f"{name}: at most {MAX_EVAL_JOINTS} joints, got {labels.shape[1]}")
+        if labels.shape[0] > MAX_DEV_FRAMES:
+            raise ValueError(f"{name}: at most {MAX_DEV_FRAMES} frames a call, got {labels.shape[0]}")
+        if shape_only:
+            return labels
+        if not labels.is_cuda:
+            raise TypeError(f"{name} must be a CUDA (ROCm) tensor")
+        return labels.detach().float().contiguous()
+
+    def calculateCoMfrom3DJoints(self, jnts, scale=None, stream=None, out=None):
+        """``tfMonkeyDetector.calculateCoMfrom3DJoints`` (tf_monkeydetector.py:66-71) of labels
+        [n, J, 3] in mm, then the driver's normalisation ``/ scale`` (train_cnn_networks_hgru.py:166,
+        ``scale = (orig0, orig1, max_depth)``; ``None``: the plain uvd) -> [n, 3] float32.
+
+        All float32: the mean over the joints is ``labels.mean(axis=1)`` (a sequential sum in joint
+        order, divided by f32(J)); then TF's ``xyztouvd``, ``u = f32(ux) - (x / z) * f32(fx)``,
+        ``v = f32(uy) + (y / z) * f32(fy)``, ``d = -z`` with no ``z == 0`` guard (inf / NaN propagate
+        as in TF); then ``/ f32(scale[k])``.  numpy in -> these operations on the host (the CPU oracle
+        of the kernel); a CUDA tensor in -> ``mp_com_from_joints_dev``, the same bits.  TF's own
+        ``reduce_mean`` order over the joints is PARITY UNPINNED (no TensorFlow here); every other
+        operation is elementwise."""
+        sc = (1.0, 1.0, 1.0) if scale is None else tuple(float(v) for v in scale)
+        if len(sc) != 3:
+            raise ValueError("scale must have three entries (u, v, d)")
+        if isinstance(jnts, np.ndarray) or not hasattr(jnts, "is_cuda"):
+            j = np.asarray(jnts, np.float32)
+            if j.ndim != 3 or j.shape[2] != 3 or 0 in j.shape:
+                raise ValueError(f"jnts must be [n, joints, 3], got {j.shape}")
+            f32 = np.float32
+            with np.errstate(divide="ignore", invalid="ignore"):
+                m = j.mean(axis=1, dtype=np.float32)
+                u = f32(self.ux) - (m[:, 0] / m[:, 2]) * f32(self.fx)
+                v = f32(self.uy) + (m[:, 1] / m[:, 2]) * f32(self.fy)
+                d = -m[:, 2]
+                return np.stack([u / f32(sc[0]), v / f32(sc[1]), d / f32(sc[2])], axis=1).astype(np.float32)
+        import torch
+        lab = self._dev_labels(jnts, "jnts")
+        n, J = lab.shape[0], lab.shape[1]
+        if out is None:
+            out = torch.empty((n, 3), dtype=torch.float32, device=lab.device)
+        st = _lib.current_stream(lab.device) if stream is None else stream
+        cam = self._cam()
+        _lib.check(_lib_crop().mp_com_from_joints_dev(ctypes.byref(cam), ctypes.c_void_p(lab.data_ptr()), n, J,
+                                                      sc[0], sc[1], sc[2], ctypes.c_void_p(out.data_ptr()),
+                                                      ctypes.c_void_p(st)))
+        return out
+
+    calculateCoMfrom3DJoints_device = calculateCoMfrom3DJoints
+
+    def relative_labels(self, labels_xyz, coms):
+        """The label half of ``prepare_data`` (train_cnn_networks_hgru.py:52-56) on the host: labels
+        [n, J, 3] float32 in mm, coms [n, 3] (u, v, d) -> [n, 3J] float32 =
+        ``clip((label - uvdtoxyz(com)) / f32(cube_z / 2), -1, 1)`` (``getRelativeCoordinates``'s
+        rel_xyz; rel_uvd is plot-only in the reference and not produced)."""
+        lab = np.asarray(labels_xyz, np.float32)
+        n = lab.shape[0]
+        lab = lab.reshape(n, -1, 3)
+        c = self.uvdtoxyz(np.asarray(coms, np.float64).reshape(n, 3))          # float64 ops, one rounding
+        rel = (lab - c[:, None, :]) / np.float32(self.cube[2] / 2.)
+        return np.clip(rel, np.float32(-1), np.float32(1)).reshape(n, -1)
+
+    def relative_labels_device(self, labels_xyz, coms, stream=None, out=None, num_joints=None):
+        """``relative_labels`` on the GPU (``mp_rel_labels_dev``): ``labels_xyz`` CUDA [n, J, 3] fp32 in
+        mm (or [n, 3J] with ``num_joints``), ``coms`` CUDA [n, 3] f64 (the crop's coms) -> CUDA
+        [n, 3J] fp32, the bits of the host function; asynchronous, a NaN label stays NaN."""
+        import torch
+        lab = self._dev_labels(labels_xyz, "labels_xyz", num_joints, shape_only=True)
+        n, J = lab.shape[0], lab.shape[1]
+        if isinstance(coms, torch.Tensor) and tuple(coms.shape) != (n, 3):
+            raise ValueError(f"coms must be [{n}, 3], got {tuple(coms.shape)}")
+        lab = self._dev_labels(lab, "labels_xyz")
+        c = self._dev_coms(coms, n)
+        if out is None:
+            out = torch.empty((n, 3 * J), dtype=torch.float32, device=lab.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32
+                  and out.is_contiguous() and out.numel() == n * 3 * J):
+            raise ValueError(f"out must be a contiguous CUDA float32 tensor of {n * 3 * J} elements")
+        st = _lib.current_stream(lab.device) if stream is None else stream
+        cam = self._cam()
+        _lib.check(_lib_crop().mp_rel_labels_dev(ctypes.byref(cam), ctypes.c_void_p(lab.data_ptr()), n, J,
+                                                 ctypes.c_void_p(c.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                                 ctypes.c_void_p(st)))
+        return out
 
     # ------------------------------------------------------------------ geometry (host numpy)
     def comToBounds(self, com, size):

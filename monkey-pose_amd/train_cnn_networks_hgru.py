@@ -11,6 +11,11 @@
   crop (``mp_crop3d_batch``).
 * ``FramePosePipeline``: ``test_model``'s per-batch body (284-321) -- attention, device crop,
   hGRU pose regressor -- as one device-resident call.
+* ``prepare_data(images, labels, tr_res, md, config)`` (41-59): ``prepare_data_test`` plus the label
+  half (relative labels, ``mp_rel_labels_dev``); ``calc_com_error`` (36-39); ``ValidationPipeline``
+  / ``evaluate_tfrecord``: the validation pass of ``train_model`` (160-173, 229-237) for labelled
+  batches -- attention, crop + relative labels, pose, joint errors and metrics accumulated in device
+  memory (``pose_evaluation.PoseEvaluator``), no host round trip.
 * ``cnn_model_struct().build(crops, num_classes)`` -> ``.out_put`` [N, num_classes]
   (train_cnn_networks_hgru.py:626-760): the regressor the reference's driver builds for
   validation (169), ``test_model`` (291) and ``eval_model_on_real_data`` (363) -- five conv +
@@ -137,6 +142,60 @@ def prepare_data_test(image_np, tr_res, md, config, dsize: Optional[int] = None)
     return patches, list(coms), [np.asmatrix(m) for m in Ms]
 
 
+def _is_cuda(x):
+    return hasattr(x, "is_cuda") and not isinstance(x, np.ndarray) and x.is_cuda
+
+
+def prepare_data(image_np, image_label_shaped, tr_res, md, config, show=False, check=True):
+    """``prepare_data`` (train_cnn_networks_hgru.py:41-59): returns (patches [N, 128, 128, 1] =
+    cropArea3D(image * max_depth, tr_res * [orig0, orig1, max_depth]) / max_depth, rel_labels
+    [N, 3J] = clip(getRelativeCoordinates(label, com).xyz / (cube_z / 2), -1, 1)), float32 holding
+    the reference's values.  The batch is ``image_np.shape[0]`` (the reference's
+    ``config.train_batch`` only sizes its arrays).
+
+    CUDA tensors in -> ``crop_batch_device`` and ``mp_rel_labels_dev``, nothing leaves the device
+    (``check``: read the crop status back, the one sync); numpy in -> the native host crop and the
+    host label half.  ``show=True`` (the reference's plot of every crop) raises."""
+    if show:
+        raise NotImplementedError("show=True plots every crop in the reference; plotting is out of scope")
+    if _is_cuda(image_np):
+        patches, rel, _, _ = _prepare_data_device(image_np, image_label_shaped, tr_res, md, config, check)
+        return patches, rel
+    patches, coms, _ = prepare_data_test(image_np, tr_res, md, config)
+    lab = np.asarray(image_label_shaped, np.float32)
+    if lab.shape[0] != patches.shape[0]:
+        raise ValueError(f"{patches.shape[0]} frames but {lab.shape[0]} label rows")
+    return patches, md.relative_labels(lab, np.stack(coms))
+
+
+def _prepare_data_device(frames, labels, tr_res, md, config, check):
+    """prepare_data on the device -> (patches, rel_labels, coms [n, 3] f64, Ms [n, 3, 3] f64)"""
+    n = frames.shape[0]
+    J = int(getattr(config, "num_joints", 0)) or None
+    lab = md._dev_labels(labels, "image_label_shaped", J)     # raises before any GPU call
+    if lab.shape[0] != n:
+        raise ValueError(f"{n} frames but {lab.shape[0]} label rows")
+    scale = (float(config.image_orig_size[0]), float(config.image_orig_size[1]), float(config.image_max_depth))
+    patches, Ms, coms = md.crop_batch_device(frames, tr_res, com_scale=scale,
+                                             frame_scale=float(config.image_max_depth),
+                                             dsize=int(config.image_target_size[0]), check=check)
+    return patches, md.relative_labels_device(lab, coms), coms, Ms
+
+
+def calc_com_error(labels, predictions):
+    """``calc_com_error`` (train_cnn_networks_hgru.py:36-39): the mean over the batch of the
+    distance between [n, 3] (u, v, d) rows; numpy in -> float32 numpy, CUDA tensors in -> the
+    device evaluator with one joint (float64)."""
+    assert tuple(labels.shape) == tuple(predictions.shape)
+    from . import pose_evaluation as PE
+    if _is_cuda(labels) or _is_cuda(predictions):
+        if labels.dim() != 2 or labels.shape[1] != 3:
+            raise ValueError(f"labels must be [n, 3], got {tuple(labels.shape)}")
+        return PE.getMeanError_np(labels[:, None, :], predictions[:, None, :])
+    lab, pred = np.asarray(labels), np.asarray(predictions)
+    return np.nanmean(np.sqrt(np.square(lab - pred).sum(axis=1)), axis=0)
+
+
 class FramePosePipeline:
     """``test_model``'s per-batch body (train_cnn_networks_hgru.py:284-321) on one GPU:
     frames -> attention CoM -> device crop -> hGRU pose, no host round trip in between.
@@ -157,8 +216,86 @@ class FramePosePipeline:
         patches, Ms, coms = self.md.crop_batch_device(
             frames, com_norm, com_scale=(cfg.image_orig_size[0], cfg.image_orig_size[1], cfg.image_max_depth),
             frame_scale=float(cfg.image_max_depth), dsize=cfg.image_target_size[0], check=self.check_crops)
-        out = self.pose.build(patches, cfg.num_classes, h2_init=h2_init)
+        kw = {} if h2_init is None else {"h2_init": h2_init}    # cnn_model_struct has no hidden state
+        out = self.pose.build(patches, cfg.num_classes, **kw)
         return out, coms, Ms
+
+
+class ValidationPipeline:
+    """The validation pass of ``train_model`` (train_cnn_networks_hgru.py:160-173, 229-237) and of
+    ``test_model``'s loop for a labelled batch on one GPU: frames + labels -> attention CoM -> device
+    crop + relative labels (``prepare_data``) -> pose regressor -> joint error in mm, accumulated in
+    two device-resident evaluators (``pose_evaluation.PoseEvaluator``):
+
+    * ``pose``: rel_labels against the pose output, both at scale ``cube_z / 2`` --
+      ``getMeanError_train(val_crop_labels_shaped, val_results_shaped)`` (171-173);
+    * ``com`` (one joint): ``calculateCoMfrom3DJoints(labels) / (orig0, orig1, max_depth)`` against
+      the attention output -- ``calc_com_error(val_com2d, attn_val_results_shaped)`` (165-167).
+
+    ``run(frames, labels, h2_init=None)``: ``frames`` CUDA [n, h, w, 1] fp32 normalised as for
+    ``FramePosePipeline``, ``labels`` CUDA [n, 3J] or [n, J, 3] fp32 in mm -> (out [n, 3J],
+    rel_labels [n, 3J], coms [n, 3] f64, Ms [n, 3, 3] f64).  Nothing leaves the device; the only
+    sync is the crop status read when ``check_crops`` is set.  ``summary()`` ->
+    ``{"pose": {...}, "com": {...}}`` (``PoseEvaluator.summary``); ``reset()`` starts over."""
+
+    def __init__(self, attn: attn_model_struct, pose_model, md, config: Optional[InferenceConfig] = None,
+                 thresholds=range(100), check_crops: bool = True):
+        from .pose_evaluation import PoseEvaluator
+        self.attn, self.pose, self.md = attn, pose_model, md
+        self.config = config or InferenceConfig()
+        self.check_crops = bool(check_crops)
+        self.pose_eval = PoseEvaluator(self.config.num_joints, thresholds)
+        self.com_eval = PoseEvaluator(1, thresholds)
+
+    def run(self, frames, labels, h2_init=None):
+        import torch
+        cfg, md = self.config, self.md
+        if not (isinstance(frames, torch.Tensor) and frames.is_cuda):
+            raise TypeError("frames must be a CUDA (ROCm) tensor")
+        lab = md._dev_labels(labels, "labels", cfg.num_joints)          # shape, then device: before any GPU call
+        if lab.shape[1] != cfg.num_joints or lab.shape[0] != frames.shape[0]:
+            raise ValueError(f"labels must be [{frames.shape[0]}, {cfg.num_joints}, 3], got {tuple(lab.shape)}")
+        com_norm = self.attn.build(frames, cfg.num_dims)
+        patches, rel, coms, Ms = _prepare_data_device(frames, lab, com_norm, md, cfg, self.check_crops)
+        kw = {} if h2_init is None else {"h2_init": h2_init}
+        if getattr(self.pose, "_ctx", None) is None:
+            out = self.pose.build(patches, cfg.num_classes, **kw)
+        else:
+            out = self.pose.forward(patches, **kw)
+        self.pose_eval.update(rel, out, scale=float(md.cube[2]) / 2.0)
+        scale = (cfg.image_orig_size[0], cfg.image_orig_size[1], cfg.image_max_depth)
+        com2d = md.calculateCoMfrom3DJoints(lab, scale=scale)
+        self.com_eval.update(com2d[:, None, :], com_norm[:, None, :cfg.num_dims])
+        return out, rel, coms, Ms
+
+    def summary(self):
+        return {"pose": self.pose_eval.summary(), "com": self.com_eval.summary()}
+
+    def reset(self):
+        self.pose_eval.reset()
+        self.com_eval.reset()
+
+
+def evaluate_tfrecord(tfrecord_file, pipeline: ValidationPipeline, batch_size, max_batches=None, device=None):
+    """One epoch of ``data_loader.inputs(tfrecord_file, shuffle=False, device=...)`` (frames in mm as
+    the reference's records hold them, labels [3J] in mm) through ``pipeline`` (reset first):
+    frames / image_max_depth as the driver feeds them (161), then ``pipeline.run``.  Returns
+    ``pipeline.summary()``; a partial last batch is dropped as ``shuffle_batch`` does."""
+    import torch
+    from . import data_loader as DL
+    cfg = pipeline.config
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    pipeline.reset()
+    done = 0
+    for frames, labels in DL.inputs(tfrecord_file, 1, cfg.image_orig_size, [cfg.num_classes], int(batch_size),
+                                    shuffle=False, device=dev):
+        if max_batches is not None and done >= int(max_batches):
+            break
+        pipeline.run(frames / float(cfg.image_max_depth), labels)
+        done += 1
+    if done == 0:
+        raise ValueError(f"{tfrecord_file}: fewer records than one batch of {batch_size}")
+    return pipeline.summary()
 
 
 class DetectorPosePipeline:
