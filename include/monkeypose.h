@@ -305,6 +305,24 @@ int mp_crop3d_dev_coms(const mp_camera* cam, const float* frames, int64_t n, int
                        const double* coms, int flags, int64_t dsize, float* patches, double* Ms, double* coms_out,
                        int32_t* status, void* stream);
 
+/* The two calls above by frame element type (added after 0.3; mp_version() is unchanged).
+ * MP_DEPTH_F32 forwards to them.  MP_DEPTH_U16: frames are uint16 millimetres [n][h][w] in device
+ * memory (2-byte aligned; a camera's frames uploaded as they are, half the bytes), computed with
+ * the uint16 semantics of the host functions and bit-identical to mp_center_of_mass(MP_DEPTH_U16) /
+ * mp_crop3d_batch / mp_crop3d_ex(MP_DEPTH_U16): thresholds compared in float64, an exact integer
+ * depth sum, a truncating near-plane clamp, and a docom refinement whose sums are all integers.
+ * uint16 frames have no normalised form: frame_scale must be 1.0f.  That, a frames pointer at an
+ * odd address and an unknown depth_dtype are MP_ERR_ARG (the work-size query returns 0); shape
+ * limits, work-buffer rules, outputs and status codes are those of the float32 calls.  Every
+ * argument is validated before the first GPU call. */
+size_t mp_center_of_mass_dev_work_dt(int depth_dtype, int64_t n, int64_t h, int64_t w);
+int mp_center_of_mass_dev_dt(const mp_camera* cam, const void* frames, int depth_dtype, int64_t n, int64_t h,
+                             int64_t w, float frame_scale, double* coms, void* work, size_t work_bytes,
+                             void* stream);
+int mp_crop3d_dev_coms_dt(const mp_camera* cam, const void* frames, int depth_dtype, int64_t n, int64_t h, int64_t w,
+                          float frame_scale, const double* coms, int flags, int64_t dsize, float* patches,
+                          double* Ms, double* coms_out, int32_t* status, void* stream);
+
 /* getAbsoluteCoordinates (monkeydetector.py:356-360) of a pose output: pose [n][joints * 3] float32
  * normalised by cube_z / 2 (the regressors' output), coms [n][3] float64 (u, v, d).  Per joint:
  * xyz = pose * f32(cube_z / 2) + f32(uvdtoxyz(com)) in mm, uvd = xyztouvd(xyz) (a joint with z == 0

@@ -12,11 +12,16 @@
 //   com_finish_kernel   one block per frame: the chunk sums added level by level (the complete top
 //                       of numpy's recursion), the integer sums added, then the float64 operations
 //                       of mp_crop.hip's center_of_mass.
+//   com_u16_chunk_kernel / com_u16_finish_kernel
+//                       calculateCoM of uint16 frames: the threshold of depth_u16.hpp as integer
+//                       bounds, integer sums only (exact in any order), then the same float64 lines.
 //   abs_joints_kernel   getAbsoluteCoordinates (monkeydetector.py:356-360) per joint.
 //
-// Bit-exact with the host mp_center_of_mass(MP_DEPTH_F32) / MonkeyDetector.getAbsoluteCoordinates:
-// every float operation is the host's, in its order; contraction is off.
+// Bit-exact with the host mp_center_of_mass(MP_DEPTH_F32 / MP_DEPTH_U16) /
+// MonkeyDetector.getAbsoluteCoordinates: every float operation is the host's, in its order;
+// contraction is off.
 #include "com_plan.hpp"
+#include "depth_u16.hpp"
 #include "mp_kernels.hpp"
 
 #pragma clang fp contract(off)
@@ -212,6 +217,121 @@ hipError_t launch_center_of_mass(const float* frames, int N, int H, int W, float
   hipLaunchKernelGGL(com_chunk_kernel, dim3((unsigned)P, (unsigned)N), dim3(COM_T), 0, st, frames, hw, W,
                      frame_scale, lo_t, hi_t, Dc, part, isum);
   hipLaunchKernelGGL(com_finish_kernel, dim3((unsigned)N), dim3(COM_T), 0, st, part, isum, Dc, coms);
+  return hipGetLastError();
+}
+
+// ---- calculateCoM of uint16 frames (mp_center_of_mass(MP_DEPTH_U16)) -------------------------------
+// Every sum of a uint16 frame is an integer (numpy's dc.sum() of a uint16 array is exact), so any
+// partition gives the host's bits: no LDS tile, no pairwise plan.  A frame's h * w pixels are cut
+// into chunks of U16_CHUNK, one block each (the float32 kernel's bytes per block).  The chunk is read
+// with 16-byte loads (8 pixels) between a scalar head up to the first 16-byte boundary and a scalar
+// tail: frame f starts at byte 2 * f * h * w of a buffer that may itself start at any even byte.
+// Five integer sums per thread, wave shuffles, LDS, one record per chunk in the work buffer.
+constexpr int U16_CHUNK = 8192;
+constexpr int U16_SUMS = 5;   // positive count, row sum, column sum, non-zero count, value sum
+
+__global__ __launch_bounds__(COM_T) void com_u16_chunk_kernel(const uint16_t* __restrict__ frames, int64_t hw, int W,
+                                                              mpu16::ComBounds th, int P, u64* __restrict__ isum) {
+  __shared__ u64 wsum[COM_T / 64][U16_SUMS];
+  const int t = threadIdx.x;
+  const int64_t f = blockIdx.y, c = blockIdx.x;
+  const int64_t lo = c * U16_CHUNK;                                      // < hw: P = ceil(hw / U16_CHUNK)
+  const int m = (int)(hw - lo < U16_CHUNK ? hw - lo : (int64_t)U16_CHUNK);
+  const uint16_t* src = frames + f * hw + lo;
+
+  unsigned np = 0, nz = 0;
+  u64 sy = 0, sx = 0, sv = 0;
+  auto take = [&](uint16_t raw, unsigned y, unsigned x) {
+    const unsigned v = mpu16::com_out(raw, th) ? 0u : (unsigned)raw;   // dc[dc < min] = 0; dc[dc > max] = 0
+    const bool pos = v > 0u;
+    np += pos;
+    sy += pos ? y : 0u;
+    sx += pos ? x : 0u;
+    nz += v != 0u;
+    sv += v;
+  };
+  const unsigned uw = (unsigned)W;
+  // block-uniform: the pixels before the first 16-byte boundary (src is 2-byte aligned)
+  int head = (int)(((16 - (reinterpret_cast<uintptr_t>(src) & 15)) & 15) >> 1);
+  if (head > m) head = m;
+  const int nv = (m - head) / 8;
+  for (int v8 = t; v8 < nv; v8 += COM_T) {
+    const uint4 q = *reinterpret_cast<const uint4*>(src + head + 8 * v8);
+    const unsigned idx = (unsigned)(lo + head + 8 * v8);   // h * w <= 2^30
+    unsigned y = idx / uw, x = idx - y * uw;
+    const unsigned e[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      take((uint16_t)(e[k >> 1] >> (16 * (k & 1))), y, x);
+      if (++x == uw) {
+        x = 0;
+        ++y;
+      }
+    }
+  }
+  // the head (t < head) and the tail (the last (m - head) % 8): at most 7 pixels each
+  const int i = t < head ? t : head + 8 * nv + (t - head);
+  if (i < m) {
+    const unsigned idx = (unsigned)(lo + i);
+    const unsigned y = idx / uw;
+    take(src[i], y, idx - y * uw);
+  }
+
+  u64 acc[U16_SUMS] = {(u64)np, sy, sx, (u64)nz, sv};
+#pragma unroll
+  for (int k = 0; k < U16_SUMS; ++k) acc[k] = wave_sum(acc[k]);
+  if ((t & 63) == 0)
+    for (int k = 0; k < U16_SUMS; ++k) wsum[t / 64][k] = acc[k];
+  __syncthreads();
+  if (t < U16_SUMS) {
+    u64 s = 0;
+    for (int wv = 0; wv < COM_T / 64; ++wv) s += wsum[wv][t];
+    isum[(f * P + c) * U16_SUMS + t] = s;
+  }
+}
+
+// one wave per frame: the chunk records added, then center_of_mass<uint16_t>'s float64 lines
+__global__ __launch_bounds__(64) void com_u16_finish_kernel(const u64* __restrict__ isum, int P,
+                                                            double* __restrict__ coms) {
+#pragma clang fp contract(off)
+  const int t = threadIdx.x;
+  const int64_t f = blockIdx.x;
+  const u64* is = isum + f * P * U16_SUMS;
+  u64 acc[U16_SUMS] = {0, 0, 0, 0, 0};
+  for (int i = t; i < P; i += 64)
+    for (int k = 0; k < U16_SUMS; ++k) acc[k] += is[(int64_t)i * U16_SUMS + k];
+#pragma unroll
+  for (int k = 0; k < U16_SUMS; ++k) acc[k] = wave_sum(acc[k]);
+  if (t == 0) {
+    const u64 npos = acc[0], sr = acc[1], sc = acc[2], num = acc[3];
+    double com[3] = {0.0, 0.0, 0.0};
+    if (num != 0) {   // mp_crop.hip center_of_mass
+      const double cc0 = (double)sr / (double)npos, cc1 = (double)sc / (double)npos;
+      const double s = (double)acc[4];
+      com[0] = (cc1 * (double)num) / (double)num;
+      com[1] = (cc0 * (double)num) / (double)num;
+      com[2] = s / (double)num;
+    }
+    coms[3 * f] = com[0];
+    coms[3 * f + 1] = com[1];
+    coms[3 * f + 2] = com[2];
+  }
+}
+
+static int64_t com_u16_chunks(int64_t hw) { return (hw + U16_CHUNK - 1) / U16_CHUNK; }
+
+size_t com_u16_work_bytes(int64_t n, int64_t hw) {
+  return (size_t)(n * com_u16_chunks(hw)) * U16_SUMS * sizeof(u64);
+}
+
+hipError_t launch_center_of_mass_u16(const uint16_t* frames, int N, int H, int W, double min_depth, double max_depth,
+                                     double* coms, void* work, hipStream_t st) {
+  const int64_t hw = (int64_t)H * W;
+  const int P = (int)com_u16_chunks(hw);   // <= 2^17
+  u64* isum = static_cast<u64*>(work);
+  hipLaunchKernelGGL(com_u16_chunk_kernel, dim3((unsigned)P, (unsigned)N), dim3(COM_T), 0, st, frames, hw, W,
+                     mpu16::com_bounds(min_depth, max_depth), P, isum);
+  hipLaunchKernelGGL(com_u16_finish_kernel, dim3((unsigned)N), dim3(64), 0, st, isum, P, coms);
   return hipGetLastError();
 }
 

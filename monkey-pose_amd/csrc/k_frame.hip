@@ -9,10 +9,15 @@
 //                           / max_depth for every frame of the batch on the device -- the
 //                           reference's per-image host loop (61-74) in one launch.  Geometry from
 //                           crop_geom.hpp (shared with the host crop, so the integers agree).
+//                           Also around given float64 CoMs (the detector path), of float32 or of
+//                           uint16 frames (depth_u16.hpp: the pixel rules shared with the host).
 //
 // Both are HBM/latency bound byte movers: one thread per output element, coalesced along the
 // innermost output axis.
+#include <type_traits>
+
 #include "crop_geom.hpp"
+#include "depth_u16.hpp"
 #include "mp_kernels.hpp"
 
 #pragma clang fp contract(off)
@@ -71,8 +76,10 @@ constexpr int CROP_PIX_PER_BLOCK = 1024;
     com[2] = c64[3 * f + 2];                                                                    \
   }
 
-template <bool F64>
-__global__ __launch_bounds__(256) void crop3d_kernel(mp_camera cam, const float* __restrict__ frames, int H, int W,
+// The frame's pixel type is the other: PX = float keeps the float32 rules below; PX = uint16_t (frames
+// in mm, frame_scale 1) applies getCrop's uint16 rule of depth_u16.hpp and widens the stored value.
+template <bool F64, typename PX>
+__global__ __launch_bounds__(256) void crop3d_kernel(mp_camera cam, const PX* __restrict__ frames, int H, int W,
                                                      float frame_scale, const float* __restrict__ com_norm,
                                                      double cs0, double cs1, double cs2, int dsz,
                                                      float* __restrict__ patches, double* __restrict__ Ms,
@@ -112,7 +119,7 @@ __global__ __launch_bounds__(256) void crop3d_kernel(mp_camera cam, const float*
   }
   __syncthreads();
   const float md = (float)cam.max_depth;
-  const float* fr = frames + (size_t)f * H * W;
+  const PX* fr = frames + (size_t)f * H * W;
   float* dst = patches + (size_t)f * dsz * dsz;
   const int npix = dsz * dsz;
   for (int k = 0; k < CROP_PIX_PER_BLOCK / 256; ++k) {
@@ -126,14 +133,19 @@ __global__ __launch_bounds__(256) void crop3d_kernel(mp_camera cam, const float*
         const int64_t sy = mpgeom::nn_row(g, y) - g.pt, sx = mpgeom::nn_col(g, x) - g.pl;
         v = 0.f;
         if (sy >= 0 && sy < g.r1 - g.r0 && sx >= 0 && sx < g.c1 - g.c0) {
-          const float d = fr[(g.r0 + sy) * W + (g.c0 + sx)] * frame_scale;   // image * max_depth (float32)
-          // float32 frame vs float64 bounds: compared in float32 (NumPy 1.x rule, crop_geom.hpp)
-          if (mpgeom::f32_lt(d, g.zstart) && d != 0.f)
-            v = (float)g.zstart;
-          else if (mpgeom::f32_gt(d, g.zend) && d != 0.f)
-            v = 0.f;
-          else
-            v = d;
+          if constexpr (std::is_same<PX, uint16_t>::value) {
+            // uint16 frame: compared in float64, zstart stored truncated (depth_u16.hpp), then widened
+            v = (float)mpu16::crop_px(fr[(g.r0 + sy) * W + (g.c0 + sx)], g.zstart, g.zend);
+          } else {
+            const float d = fr[(g.r0 + sy) * W + (g.c0 + sx)] * frame_scale;   // image * max_depth (float32)
+            // float32 frame vs float64 bounds: compared in float32 (NumPy 1.x rule, crop_geom.hpp)
+            if (mpgeom::f32_lt(d, g.zstart) && d != 0.f)
+              v = (float)g.zstart;
+            else if (mpgeom::f32_gt(d, g.zend) && d != 0.f)
+              v = 0.f;
+            else
+              v = d;
+          }
         }
       }
     }
@@ -150,6 +162,8 @@ __global__ __launch_bounds__(256) void crop3d_kernel(mp_camera cam, const float*
 // n / 2^D >= 160, since a split loses at most 15 from the smaller half over D levels), so thread t
 // sums the subtree on its D-bit path sequentially in numpy's order and the 2^D results are combined
 // pairwise level by level, which is exactly numpy's recursion.
+// A uint16 frame's crop is a uint16 array: calculateCoM's dc.sum() is then an exact integer sum, a
+// fifth integer beside the mask sums, and there is no order to keep.
 constexpr int REF_T = 256;
 // getCrop's output (monkeydetector.py:177-213) at flat index i of the padded crop
 __device__ float crop_getcrop_value(const mpgeom::CropGeom& g, const float* fr, int W, float frame_scale, int64_t i) {
@@ -173,6 +187,21 @@ __device__ float crop_dc_value(const mpgeom::CropGeom& g, const float* fr, int W
                                const mp_camera& cam, int64_t i) {
   const float v = crop_getcrop_value(g, fr, W, frame_scale, i);
   return (mpgeom::f32_lt(v, cam.min_depth) || mpgeom::f32_gt(v, cam.max_depth)) ? 0.f : v;
+}
+
+// the same two values of a uint16 frame (depth_u16.hpp: float64 compares, uint16 stores)
+__device__ uint16_t crop_getcrop_value(const mpgeom::CropGeom& g, const uint16_t* fr, int W, float, int64_t i) {
+  const int64_t y = i / g.cols, x = i - y * g.cols;
+  const int64_t sy = y - g.pt, sx = x - g.pl;
+  if (sy >= 0 && sy < g.r1 - g.r0 && sx >= 0 && sx < g.c1 - g.c0)
+    return mpu16::crop_px(fr[(g.r0 + sy) * W + (g.c0 + sx)], g.zstart, g.zend);
+  return 0;
+}
+
+__device__ uint16_t crop_dc_value(const mpgeom::CropGeom& g, const uint16_t* fr, int W, float frame_scale,
+                                  const mp_camera& cam, int64_t i) {
+  const uint16_t v = crop_getcrop_value(g, fr, W, frame_scale, i);
+  return mpu16::com_out(v, cam.min_depth, cam.max_depth) ? (uint16_t)0 : v;
 }
 
 // numpy's pairwise float32 sum of dc[lo, lo + n), iteratively (explicit stack of pending right halves)
@@ -222,8 +251,8 @@ __device__ float pairwise_dc(const mpgeom::CropGeom& g, const float* fr, int W, 
   return vals[0];
 }
 
-template <bool F64>
-__global__ __launch_bounds__(REF_T) void crop_refine_kernel(mp_camera cam, const float* __restrict__ frames, int H,
+template <bool F64, typename PX>
+__global__ __launch_bounds__(REF_T) void crop_refine_kernel(mp_camera cam, const PX* __restrict__ frames, int H,
                                                             int W, float frame_scale, const float* __restrict__ com_norm,
                                                             double cs0, double cs1, double cs2, int dsz,
                                                             double* __restrict__ coms_out, int32_t* __restrict__ status) {
@@ -231,10 +260,13 @@ __global__ __launch_bounds__(REF_T) void crop_refine_kernel(mp_camera cam, const
   __shared__ mpgeom::CropGeom g;
   __shared__ int st;
   __shared__ float part[REF_T];
-  __shared__ long long isum[4][REF_T];
+  // a uint16 crop's value sum is a fifth integer sum (exact), in place of the pairwise float32 sum
+  constexpr bool U16 = std::is_same<PX, uint16_t>::value;
+  constexpr int NS = U16 ? 5 : 4;
+  __shared__ long long isum[NS][REF_T];
   __shared__ int D;
   const int f = blockIdx.x, t = threadIdx.x;
-  const float* fr = frames + (size_t)f * H * W;
+  const PX* fr = frames + (size_t)f * H * W;
   if (t == 0) {
     MP_CROP_COM_IN(com)
     st = mpgeom::crop_geometry(cam, com, H, W, dsz, &g);
@@ -254,26 +286,31 @@ __global__ __launch_bounds__(REF_T) void crop_refine_kernel(mp_camera cam, const
   const int64_t n = g.rows * g.cols;
   // integer sums of calculateCoM: positive count, row / column index sums, non-zero count
   long long np = 0, sy = 0, sx = 0, nz = 0;
+  [[maybe_unused]] long long sv = 0;
   for (int64_t i = t; i < n; i += REF_T) {
-    const float v = crop_dc_value(g, fr, W, frame_scale, cam, i);
-    if (v > 0.f) {
+    const PX v = crop_dc_value(g, fr, W, frame_scale, cam, i);
+    if (v > PX(0)) {
       ++np;
       sy += i / g.cols;
       sx += i % g.cols;
     }
-    nz += v != 0.f;
+    nz += v != PX(0);
+    if constexpr (U16) sv += v;
   }
   isum[0][t] = np; isum[1][t] = sy; isum[2][t] = sx; isum[3][t] = nz;
-  // the float32 pairwise sum: thread t < 2^D sums the subtree on its path
-  const int nl = 1 << D;
-  if (t < nl) {
-    int64_t lo = 0, m = n;
-    for (int b = D - 1; b >= 0; --b) {
-      int64_t n2 = m / 2;
-      n2 -= n2 % 8;
-      if ((t >> b) & 1) { lo += n2; m -= n2; } else { m = n2; }
+  if constexpr (U16) isum[4][t] = sv;
+  // the float32 pairwise sum: thread t < 2^D sums the subtree on its path (uint16: nothing to do)
+  const int nl = U16 ? 1 : 1 << D;
+  if constexpr (!U16) {
+    if (t < nl) {
+      int64_t lo = 0, m = n;
+      for (int b = D - 1; b >= 0; --b) {
+        int64_t n2 = m / 2;
+        n2 -= n2 % 8;
+        if ((t >> b) & 1) { lo += n2; m -= n2; } else { m = n2; }
+      }
+      part[t] = pairwise_dc(g, fr, W, frame_scale, cam, lo, m);
     }
-    part[t] = pairwise_dc(g, fr, W, frame_scale, cam, lo, m);
   }
   __syncthreads();
   for (int w = nl / 2; w >= 1; w /= 2) {   // combine the complete top levels in order
@@ -285,7 +322,7 @@ __global__ __launch_bounds__(REF_T) void crop_refine_kernel(mp_camera cam, const
   }
   for (int w = REF_T / 2; w >= 1; w /= 2) {   // integer sums (exact: any order)
     if (t < w)
-      for (int k = 0; k < 4; ++k) isum[k][t] += isum[k][t + w];
+      for (int k = 0; k < NS; ++k) isum[k][t] += isum[k][t + w];
     __syncthreads();
   }
   if (t == 0) {
@@ -295,7 +332,7 @@ __global__ __launch_bounds__(REF_T) void crop_refine_kernel(mp_camera cam, const
       com[0] = com[1] = com[2] = 0.0;
     } else {
       const double cc0 = (double)isum[1][0] / (double)npos, cc1 = (double)isum[2][0] / (double)npos;
-      const double s = (double)(0.f + part[0]);
+      const double s = U16 ? (double)isum[NS - 1][0] : (double)(0.f + part[0]);
       com[0] = (cc1 * (double)num) / (double)num;
       com[1] = (cc0 * (double)num) / (double)num;
       com[2] = s / (double)num;
@@ -316,15 +353,15 @@ __global__ __launch_bounds__(REF_T) void crop_refine_kernel(mp_camera cam, const
   }
 }
 
-template <bool F64>
-static hipError_t launch_crop3d_t(const mp_camera& cam, const float* frames, int N, int H, int W, float frame_scale,
+template <bool F64, typename PX>
+static hipError_t launch_crop3d_t(const mp_camera& cam, const PX* frames, int N, int H, int W, float frame_scale,
                                   const float* com_norm, const double com_scale[3], int dsz, float* patches,
                                   double* Ms, double* coms_out, int32_t* status, hipStream_t st, bool docom) {
   const int nb = (dsz * dsz + CROP_PIX_PER_BLOCK - 1) / CROP_PIX_PER_BLOCK;
   if (docom)
-    hipLaunchKernelGGL(crop_refine_kernel<F64>, dim3(N), dim3(REF_T), 0, st, cam, frames, H, W, frame_scale,
+    hipLaunchKernelGGL((crop_refine_kernel<F64, PX>), dim3(N), dim3(REF_T), 0, st, cam, frames, H, W, frame_scale,
                        com_norm, com_scale[0], com_scale[1], com_scale[2], dsz, coms_out, status);
-  hipLaunchKernelGGL(crop3d_kernel<F64>, dim3(nb, N), dim3(256), 0, st, cam, frames, H, W, frame_scale, com_norm,
+  hipLaunchKernelGGL((crop3d_kernel<F64, PX>), dim3(nb, N), dim3(256), 0, st, cam, frames, H, W, frame_scale, com_norm,
                      com_scale[0], com_scale[1], com_scale[2], dsz, patches, Ms, coms_out, status, docom ? 1 : 0);
   return hipGetLastError();
 }
@@ -332,7 +369,7 @@ static hipError_t launch_crop3d_t(const mp_camera& cam, const float* frames, int
 hipError_t launch_crop3d(const mp_camera& cam, const float* frames, int N, int H, int W, float frame_scale,
                          const float* com_norm, const double com_scale[3], int dsz, float* patches, double* Ms,
                          double* coms_out, int32_t* status, hipStream_t st, bool docom) {
-  return launch_crop3d_t<false>(cam, frames, N, H, W, frame_scale, com_norm, com_scale, dsz, patches, Ms, coms_out,
+  return launch_crop3d_t<false, float>(cam, frames, N, H, W, frame_scale, com_norm, com_scale, dsz, patches, Ms, coms_out,
                                 status, st, docom);
 }
 
@@ -341,8 +378,17 @@ hipError_t launch_crop3d_coms(const mp_camera& cam, const float* frames, int N, 
                               const double* coms, int dsz, float* patches, double* Ms, double* coms_out,
                               int32_t* status, hipStream_t st, bool docom) {
   const double unit[3] = {1.0, 1.0, 1.0};   // unused by the float64 form
-  return launch_crop3d_t<true>(cam, frames, N, H, W, frame_scale, reinterpret_cast<const float*>(coms), unit, dsz,
-                               patches, Ms, coms_out, status, st, docom);
+  return launch_crop3d_t<true, float>(cam, frames, N, H, W, frame_scale, reinterpret_cast<const float*>(coms), unit,
+                                      dsz, patches, Ms, coms_out, status, st, docom);
+}
+
+// ... of uint16 frames in mm (MP_DEPTH_U16; there is no normalised form, so no frame scale)
+hipError_t launch_crop3d_coms_u16(const mp_camera& cam, const uint16_t* frames, int N, int H, int W,
+                                  const double* coms, int dsz, float* patches, double* Ms, double* coms_out,
+                                  int32_t* status, hipStream_t st, bool docom) {
+  const double unit[3] = {1.0, 1.0, 1.0};
+  return launch_crop3d_t<true, uint16_t>(cam, frames, N, H, W, 1.0f, reinterpret_cast<const float*>(coms), unit, dsz,
+                                         patches, Ms, coms_out, status, st, docom);
 }
 
 // hidden_init 'random' (hgru_module.py:879-887) drawn on the device: element i of O0 is

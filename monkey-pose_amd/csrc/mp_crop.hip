@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "crop_geom.hpp"
+#include "depth_u16.hpp"
 #include "mp_runtime.hpp"
 
 #pragma clang fp contract(off)
@@ -72,10 +73,10 @@ inline float float_at_most(double x) {
   return f;
 }
 template <typename T>
-struct Thresh {
+struct Thresh {   // uint16: the float64 comparison of depth_u16.hpp
   double lo, hi;
   explicit Thresh(const mp_camera& c) : lo(c.min_depth), hi(c.max_depth) {}
-  bool out(T v) const { return (double)v < lo || (double)v > hi; }
+  bool out(T v) const { return mpu16::com_out(v, lo, hi); }
 };
 template <>
 struct Thresh<float> {
@@ -201,11 +202,7 @@ inline float crop_px(float v, const mpgeom::CropGeom& g) {
   if (mpgeom::f32_gt(v, g.zend) && v != 0.f) return 0.f;
   return v;
 }
-inline uint16_t crop_px(uint16_t v, const mpgeom::CropGeom& g) {
-  if ((double)v < g.zstart && v != 0) return (uint16_t)(int64_t)g.zstart;
-  if ((double)v > g.zend && v != 0) return 0;
-  return v;
-}
+inline uint16_t crop_px(uint16_t v, const mpgeom::CropGeom& g) { return mpu16::crop_px(v, g.zstart, g.zend); }
 
 // the padded, thresholded crop (getCrop's return value) at crop row y, column x
 template <typename T>
@@ -453,6 +450,67 @@ int mp_crop3d_dev_coms(const mp_camera* cam, const float* frames, int64_t n, int
                                      Ms, coms_out, status, static_cast<hipStream_t>(stream),
                                      (flags & MP_CROP_DOCOM) != 0),
               "crop3d_coms");
+  });
+}
+
+// ---- the same two calls by frame dtype: float32 forwards, uint16 runs its own kernels ------------
+size_t mp_center_of_mass_dev_work_dt(int depth_dtype, int64_t n, int64_t h, int64_t w) {
+  if (depth_dtype == MP_DEPTH_F32) return mp_center_of_mass_dev_work(n, h, w);
+  if (depth_dtype != MP_DEPTH_U16) return 0;
+  if (n <= 0 || n > 65535 || h <= 0 || w <= 0 || h * w > ((int64_t)1 << 30)) return 0;
+  return mp::com_u16_work_bytes(n, h * w);
+}
+
+// uint16 frames are millimetres: there is no normalised form to scale
+static void check_u16_frames(const char* who, const void* frames, float frame_scale) {
+  if (frame_scale != 1.0f) fail(MP_ERR_ARG, std::string(who) + ": uint16 frames take frame_scale 1");
+  if (reinterpret_cast<uintptr_t>(frames) & 1) fail(MP_ERR_ARG, std::string(who) + ": frames must be 2-byte aligned");
+}
+
+int mp_center_of_mass_dev_dt(const mp_camera* cam, const void* frames, int depth_dtype, int64_t n, int64_t h,
+                             int64_t w, float frame_scale, double* coms, void* work, size_t work_bytes,
+                             void* stream) {
+  if (depth_dtype == MP_DEPTH_F32)
+    return mp_center_of_mass_dev(cam, static_cast<const float*>(frames), n, h, w, frame_scale, coms, work, work_bytes,
+                                 stream);
+  return guard([&] {
+    if (depth_dtype != MP_DEPTH_U16) fail(MP_ERR_ARG, "mp_center_of_mass_dev_dt: unknown depth dtype");
+    check_cam(cam);
+    if (!frames || !coms || !work) fail(MP_ERR_ARG, "mp_center_of_mass_dev_dt: null pointer");
+    check_u16_frames("mp_center_of_mass_dev_dt", frames, frame_scale);
+    check_dev_frames("mp_center_of_mass_dev_dt", n, h, w);
+    if (work_bytes < mp::com_u16_work_bytes(n, h * w))
+      fail(MP_ERR_ARG, "mp_center_of_mass_dev_dt: work buffer smaller than mp_center_of_mass_dev_work_dt()");
+    if (reinterpret_cast<uintptr_t>(work) & 7)
+      fail(MP_ERR_ARG, "mp_center_of_mass_dev_dt: work must be 8-byte aligned");
+    hip_check(mp::launch_center_of_mass_u16(static_cast<const uint16_t*>(frames), (int)n, (int)h, (int)w,
+                                            cam->min_depth, cam->max_depth, coms, work,
+                                            static_cast<hipStream_t>(stream)),
+              "center_of_mass_u16");
+  });
+}
+
+int mp_crop3d_dev_coms_dt(const mp_camera* cam, const void* frames, int depth_dtype, int64_t n, int64_t h, int64_t w,
+                          float frame_scale, const double* coms, int flags, int64_t dsize, float* patches,
+                          double* Ms, double* coms_out, int32_t* status, void* stream) {
+  if (depth_dtype == MP_DEPTH_F32)
+    return mp_crop3d_dev_coms(cam, static_cast<const float*>(frames), n, h, w, frame_scale, coms, flags, dsize,
+                              patches, Ms, coms_out, status, stream);
+  return guard([&] {
+    if (depth_dtype != MP_DEPTH_U16) fail(MP_ERR_ARG, "mp_crop3d_dev_coms_dt: unknown depth dtype");
+    check_cam(cam);
+    if (flags & ~MP_CROP_DOCOM) fail(MP_ERR_ARG, "mp_crop3d_dev_coms_dt: unknown flags");
+    if (!frames || !coms || !patches || !Ms || !coms_out || !status)
+      fail(MP_ERR_ARG, "mp_crop3d_dev_coms_dt: null pointer");
+    if (coms == coms_out) fail(MP_ERR_ARG, "mp_crop3d_dev_coms_dt: coms and coms_out must not alias");
+    check_u16_frames("mp_crop3d_dev_coms_dt", frames, frame_scale);
+    check_dev_frames("mp_crop3d_dev_coms_dt", n, h, w);
+    if (dsize <= 0 || dsize > 4096) fail(MP_ERR_SHAPE, "mp_crop3d_dev_coms_dt: bad shape");
+    if (!(cam->max_depth != 0.0)) fail(MP_ERR_ARG, "camera max_depth must be non-zero");
+    hip_check(mp::launch_crop3d_coms_u16(*cam, static_cast<const uint16_t*>(frames), (int)n, (int)h, (int)w, coms,
+                                         (int)dsize, patches, Ms, coms_out, status,
+                                         static_cast<hipStream_t>(stream), (flags & MP_CROP_DOCOM) != 0),
+              "crop3d_coms_u16");
   });
 }
 

@@ -161,8 +161,15 @@ hipError_t launch_crop3d(const mp_camera& cam, const float* frames, int N, int H
 hipError_t launch_crop3d_coms(const mp_camera& cam, const float* frames, int N, int H, int W, float frame_scale,
                               const double* coms, int dsz, float* patches, double* Ms, double* coms_out,
                               int32_t* status, hipStream_t st, bool docom = false);
+// uint16 frames in mm (MP_DEPTH_U16): getCrop's uint16 rule, the refinement's sums all integers
+hipError_t launch_crop3d_coms_u16(const mp_camera& cam, const uint16_t* frames, int N, int H, int W,
+                                  const double* coms, int dsz, float* patches, double* Ms, double* coms_out,
+                                  int32_t* status, hipStream_t st, bool docom = false);
 // k_detect.hip (the detector path: full-frame calculateCoM, getAbsoluteCoordinates)
 size_t com_work_bytes(int64_t n, int64_t hw);
+size_t com_u16_work_bytes(int64_t n, int64_t hw);
+hipError_t launch_center_of_mass_u16(const uint16_t* frames, int N, int H, int W, double min_depth, double max_depth,
+                                     double* coms, void* work, hipStream_t st);
 hipError_t launch_center_of_mass(const float* frames, int N, int H, int W, float frame_scale, float lo_t,
                                  float hi_t, double* coms, void* work, hipStream_t st);
 hipError_t launch_abs_joints(const mp_camera& cam, const float* pose, int64_t n, int joints, const double* coms,

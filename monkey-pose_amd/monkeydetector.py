@@ -51,6 +51,17 @@ _CROP_SIGS = {
                                           ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_int,
                                           ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_void_p]),
+    # the same two calls by frame dtype (MP_DEPTH_F32 forwards; MP_DEPTH_U16: uint16 mm frames)
+    "mp_center_of_mass_dev_work_dt": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                                        ctypes.c_int64]),
+    "mp_center_of_mass_dev_dt": (ctypes.c_int, [ctypes.POINTER(_Camera), ctypes.c_void_p, ctypes.c_int,
+                                                ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_float,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                ctypes.c_void_p]),
+    "mp_crop3d_dev_coms_dt": (ctypes.c_int, [ctypes.POINTER(_Camera), ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+                                             ctypes.c_int64, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p,
+                                             ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "mp_abs_joints_dev": (ctypes.c_int, [ctypes.POINTER(_Camera), ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     # the validation pass on the device (k_eval.hip)
@@ -75,6 +86,7 @@ _CROP_SIGS = {
 MAX_EVAL_JOINTS = 128       # eval_plan.hpp MAX_JOINTS: numpy's pairwise sum is one leaf up to there
 MAX_EVAL_THRESHOLDS = 1024
 MAX_DEV_FRAMES = 65535
+DEPTH_F32, DEPTH_U16 = 0, 1    # monkeypose.h MP_DEPTH_*
 
 _CROP_MSG = {1: "CoM depth is zero or not finite (no valid pixel in range?)", 2: "empty crop",
              3: "degenerate bounds", 4: "resize target is empty"}
@@ -230,10 +242,13 @@ class MonkeyDetector(object):
 
     # ------------------------------------------------------------------ detector path on the device
     @staticmethod
-    def _dev_frames(frames, coms=None):
-        """``frames`` ([n, h, w] or [n, h, w, 1]) as a contiguous fp32 CUDA [n, h, w] tensor; the
-        shapes (also of ``coms`` [n, 3], when given) are checked first, then the device, both before
-        any GPU call."""
+    def _dev_frames(frames, coms=None, frame_scale=1.0):
+        """``frames`` ([n, h, w] or [n, h, w, 1]) as (a contiguous CUDA [n, h, w] tensor, its
+        MP_DEPTH_* code): a ``torch.uint16`` tensor (the camera's own millimetres) stays uint16 and
+        keeps its numpy semantics as on the host (``_frame``), every other dtype is computed as
+        fp32.  The shapes (also of ``coms`` [n, 3], when given) are checked first, then that uint16
+        frames come with ``frame_scale`` 1 (they have no normalised form), then the device, all
+        before any GPU call."""
         import torch
         if not isinstance(frames, torch.Tensor):
             raise TypeError("frames must be a CUDA (ROCm) tensor")
@@ -245,9 +260,14 @@ class MonkeyDetector(object):
             raise ValueError(f"frames must be [n, h, w], got {tuple(frames.shape)}")
         if isinstance(coms, torch.Tensor) and tuple(coms.shape) != (frames.shape[0], 3):
             raise ValueError(f"coms must be [{frames.shape[0]}, 3], got {tuple(coms.shape)}")
+        u16 = frames.dtype == torch.uint16
+        if u16 and float(frame_scale) != 1.0:
+            raise ValueError(f"uint16 frames are millimetres: frame_scale must be 1, got {frame_scale}")
         if not frames.is_cuda:
             raise TypeError("frames must be a CUDA (ROCm) tensor")
-        return frames.detach().float().contiguous()
+        if u16:
+            return frames.detach().contiguous(), DEPTH_U16
+        return frames.detach().float().contiguous(), DEPTH_F32
 
     @staticmethod
     def _dev_coms(coms, n):
@@ -260,10 +280,11 @@ class MonkeyDetector(object):
             raise TypeError("coms must be a CUDA (ROCm) tensor")
         return coms.detach().double().contiguous()
 
-    def _detect_buffers(self, n, h, w, dsize, dev):
-        """output and scratch tensors of one detector batch (``DetectorPosePipeline`` keeps them)"""
+    def _detect_buffers(self, n, h, w, dsize, dev, dt=DEPTH_F32):
+        """output and scratch tensors of one detector batch of frames of dtype code ``dt``
+        (``DetectorPosePipeline`` keeps them)"""
         import torch
-        nbytes = int(_lib_crop().mp_center_of_mass_dev_work(n, h, w))
+        nbytes = int(_lib_crop().mp_center_of_mass_dev_work_dt(dt, n, h, w))
         return dict(
             work=torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev), work_bytes=nbytes,
             coms0=torch.empty((n, 3), dtype=torch.float64, device=dev),
@@ -272,24 +293,24 @@ class MonkeyDetector(object):
             coms=torch.empty((n, 3), dtype=torch.float64, device=dev),
             status=torch.empty((n,), dtype=torch.int32, device=dev))
 
-    def _com_into(self, fr, frame_scale, coms, work, work_bytes, st):
+    def _com_into(self, fr, frame_scale, coms, work, work_bytes, st, dt=DEPTH_F32):
         n, h, w = fr.shape
         cam = self._cam()
-        _lib.check(_lib_crop().mp_center_of_mass_dev(ctypes.byref(cam), ctypes.c_void_p(fr.data_ptr()), n, h, w,
-                                                     float(frame_scale), ctypes.c_void_p(coms.data_ptr()),
-                                                     ctypes.c_void_p(work.data_ptr()), work_bytes,
-                                                     ctypes.c_void_p(st)))
+        _lib.check(_lib_crop().mp_center_of_mass_dev_dt(ctypes.byref(cam), ctypes.c_void_p(fr.data_ptr()), dt, n, h,
+                                                        w, float(frame_scale), ctypes.c_void_p(coms.data_ptr()),
+                                                        ctypes.c_void_p(work.data_ptr()), work_bytes,
+                                                        ctypes.c_void_p(st)))
 
-    def _crop_coms_into(self, fr, frame_scale, coms_in, dsize, docom, b, st):
+    def _crop_coms_into(self, fr, frame_scale, coms_in, dsize, docom, b, st, dt=DEPTH_F32):
         n, h, w = fr.shape
         cam = self._cam()
-        _lib.check(_lib_crop().mp_crop3d_dev_coms(ctypes.byref(cam), ctypes.c_void_p(fr.data_ptr()), n, h, w,
-                                                  float(frame_scale), ctypes.c_void_p(coms_in.data_ptr()),
-                                                  1 if docom else 0, int(dsize),
-                                                  ctypes.c_void_p(b["patches"].data_ptr()),
-                                                  ctypes.c_void_p(b["Ms"].data_ptr()),
-                                                  ctypes.c_void_p(b["coms"].data_ptr()),
-                                                  ctypes.c_void_p(b["status"].data_ptr()), ctypes.c_void_p(st)))
+        _lib.check(_lib_crop().mp_crop3d_dev_coms_dt(ctypes.byref(cam), ctypes.c_void_p(fr.data_ptr()), dt, n, h, w,
+                                                     float(frame_scale), ctypes.c_void_p(coms_in.data_ptr()),
+                                                     1 if docom else 0, int(dsize),
+                                                     ctypes.c_void_p(b["patches"].data_ptr()),
+                                                     ctypes.c_void_p(b["Ms"].data_ptr()),
+                                                     ctypes.c_void_p(b["coms"].data_ptr()),
+                                                     ctypes.c_void_p(b["status"].data_ptr()), ctypes.c_void_p(st)))
 
     def _check_status(self, status):
         import torch
@@ -301,35 +322,37 @@ class MonkeyDetector(object):
 
     def calculateCoM_device(self, frames, frame_scale=1.0, stream=None):
         """``calculateCoM`` (monkeydetector.py:66-83) of every frame of a CUDA batch [n, h, w] (or
-        [n, h, w, 1]) fp32 in one asynchronous call (``mp_center_of_mass_dev``): a CUDA [n, 3] float64
+        [n, h, w, 1]) in one asynchronous call (``mp_center_of_mass_dev_dt``): a CUDA [n, 3] float64
         tensor, each row the bits of ``calculateCoM(frame * frame_scale)`` (``frame_scale`` 1 for
-        frames in mm, 10000 for normalised frames)."""
-        fr = self._dev_frames(frames)
+        frames in mm, 10000 for normalised frames).  ``torch.uint16`` frames (mm, ``frame_scale`` 1)
+        give the bits of ``calculateCoM`` of the uint16 frame; any other dtype is computed as fp32."""
+        fr, dt = self._dev_frames(frames, frame_scale=frame_scale)
         import torch
         n, h, w = fr.shape
-        nbytes = int(_lib_crop().mp_center_of_mass_dev_work(n, h, w))
+        nbytes = int(_lib_crop().mp_center_of_mass_dev_work_dt(dt, n, h, w))
         work = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=fr.device)
         coms = torch.empty((n, 3), dtype=torch.float64, device=fr.device)
         st = _lib.current_stream(fr.device) if stream is None else stream
-        self._com_into(fr, frame_scale, coms, work, nbytes, st)
+        self._com_into(fr, frame_scale, coms, work, nbytes, st, dt)
         return coms
 
     def detect_crop_device(self, frames, coms=None, frame_scale=1.0, dsize=128, docom=False, check=True,
                            stream=None, _buffers=None):
         """``crop_batch`` on the GPU: ``cropArea3D(frame * frame_scale, com)`` / maxDepth per frame
-        with ``coms`` a CUDA [n, 3] float64 tensor taken as it is (``mp_crop3d_dev_coms``), or
+        with ``coms`` a CUDA [n, 3] float64 tensor taken as it is (``mp_crop3d_dev_coms_dt``), or
         ``None`` for the detector's own ``calculateCoM`` on the device first.  Returns (patches CUDA
         [n, dsize, dsize, 1], Ms CUDA [n, 3, 3] f64, coms CUDA [n, 3] f64) with the outputs, status
-        codes and ``check`` semantics of ``crop_batch_device``."""
-        fr = self._dev_frames(frames, coms)
+        codes and ``check`` semantics of ``crop_batch_device``.  ``torch.uint16`` frames (mm,
+        ``frame_scale`` 1) give the bits of ``crop_batch`` / ``cropArea3D`` of the uint16 frames."""
+        fr, dt = self._dev_frames(frames, coms, frame_scale)
         n, h, w = fr.shape
         cin = None if coms is None else self._dev_coms(coms, n)
-        b = _buffers if _buffers is not None else self._detect_buffers(n, h, w, int(dsize), fr.device)
+        b = _buffers if _buffers is not None else self._detect_buffers(n, h, w, int(dsize), fr.device, dt)
         st = _lib.current_stream(fr.device) if stream is None else stream
         if cin is None:
             cin = b["coms0"]
-            self._com_into(fr, frame_scale, cin, b["work"], b["work_bytes"], st)
-        self._crop_coms_into(fr, frame_scale, cin, dsize, docom, b, st)
+            self._com_into(fr, frame_scale, cin, b["work"], b["work_bytes"], st, dt)
+        self._crop_coms_into(fr, frame_scale, cin, dsize, docom, b, st, dt)
         self.last_status = b["status"]
         if check:
             self._check_status(b["status"])

@@ -300,16 +300,18 @@ def evaluate_tfrecord(tfrecord_file, pipeline: ValidationPipeline, batch_size, m
 
 class DetectorPosePipeline:
     """SURVEY config 5 for a batch, device-resident: ``MonkeyDetector``'s own ``calculateCoM`` of
-    every frame (``mp_center_of_mass_dev``) -> device crop around those float64 CoMs
-    (``mp_crop3d_dev_coms``) -> the pose forward -> absolute joints (``mp_abs_joints_dev``), all on
+    every frame (``mp_center_of_mass_dev_dt``) -> device crop around those float64 CoMs
+    (``mp_crop3d_dev_coms_dt``) -> the pose forward -> absolute joints (``mp_abs_joints_dev``), all on
     the current stream with no host round trip; the only sync is the status read when
     ``check_crops`` is set.  The batch counterpart of ``StreamPosePipeline`` (same bits per frame).
 
     ``pose_model``: a pose regressor with ``build(patches, num_classes, h2_init=)`` /
     ``forward(patches, h2_init=)`` (``hgru_pose.model``).  ``frame_scale``: 1 for frames in mm,
     10000 for frames normalised by the maximum depth.  ``run(frames, h2_init=None)`` with ``frames``
-    CUDA [n, h, w] or [n, h, w, 1] fp32 -> (xyz [n, J, 3] mm, uvd [n, J, 3], coms [n, 3] f64,
-    Ms [n, 3, 3] f64), CUDA tensors reused by the next call of the same batch shape."""
+    CUDA [n, h, w] or [n, h, w, 1], fp32 or ``torch.uint16`` (the camera's own millimetres, with
+    ``frame_scale`` 1: half the bytes to upload, the host's uint16 semantics) -> (xyz [n, J, 3] mm,
+    uvd [n, J, 3], coms [n, 3] f64, Ms [n, 3, 3] f64), CUDA tensors reused by the next call of the
+    same batch shape and frame dtype."""
 
     def __init__(self, pose_model, md, dsize: int = 128, num_joints: int = 23, docom: bool = False,
                  frame_scale: float = 1.0, check_crops: bool = True):
@@ -321,11 +323,12 @@ class DetectorPosePipeline:
     def run(self, frames, h2_init=None):
         import torch
         md = self.md
-        fr = md._dev_frames(frames)          # shape, then device: raises before any GPU call
+        # shape, uint16 scale, then device: raises before any GPU call
+        fr, dt = md._dev_frames(frames, frame_scale=self.frame_scale)
         n, h, w = fr.shape
-        key = (n, h, w, fr.device)
+        key = (n, h, w, fr.device, dt)
         if key != self._key:
-            self._buf = md._detect_buffers(n, h, w, self.dsize, fr.device)
+            self._buf = md._detect_buffers(n, h, w, self.dsize, fr.device, dt)
             self._out = tuple(torch.empty((n, self.num_joints, 3), dtype=torch.float32, device=fr.device)
                               for _ in range(2))
             self._key = key
