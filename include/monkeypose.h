@@ -323,6 +323,30 @@ int mp_crop3d_dev_coms_dt(const mp_camera* cam, const void* frames, int depth_dt
                           float frame_scale, const double* coms, int flags, int64_t dsize, float* patches,
                           double* Ms, double* coms_out, int32_t* status, void* stream);
 
+/* Recorded camera frames -> the attention net's input (added after 0.3; mp_version() is unchanged):
+ * the preprocessing of eval_model_on_real_data (train_cnn_networks_hgru.py:388-392, 359) for n frames
+ * in one asynchronous pass on `stream`; raw and out are device memory, nothing is allocated or
+ * synchronised.
+ *   raw         uint16 (MP_DEPTH_U16, the camera's millimetres) or float32 (MP_DEPTH_F32) frames,
+ *               aligned to their element size (a uint16 frame may start at an address that is no
+ *               multiple of 4)
+ *   transposed  1: raw is [n][w][h], as the recordings are stored (np.transpose of each, line 388);
+ *               0: raw is [n][h][w]
+ *   gate        1: g = (v < lo || v > hi) ? fill : v in the frame's own dtype -- the reference's two
+ *               masked assignments (390-391) for every fill.  uint16: integer compares; lo, hi and
+ *               fill must be integers in [0, 65535] (MP_ERR_ARG).  float32: compared against
+ *               (float)lo and (float)hi and filled with (float)fill; NaN stays NaN, +-inf is gated.
+ *               0: g = v, and lo, hi, fill are ignored
+ *   out         [n][h][w] float32 = (float)g / (float)max_depth, one correctly rounded IEEE float32
+ *               division (not a multiply by a reciprocal): numpy's bits.  4-byte aligned; 16-byte
+ *               alignment lets every row with w % 4 == 0 be stored as float4
+ * The transposed form runs 64 x 64 tiles through LDS (reads along h, stores along w), for any h, w.
+ * MP_ERR_ARG: a null or misaligned pointer, an unknown dtype, transposed or gate not 0 / 1,
+ * (float)max_depth zero or NaN; MP_ERR_SHAPE: n, h or w <= 0, n > 65535, h * w > 2^30.  Every
+ * argument is validated before the launch. */
+int mp_real_frames_dev(const void* raw, int depth_dtype, int64_t n, int64_t h, int64_t w, int transposed, int gate,
+                       double lo, double hi, double fill, double max_depth, float* out, void* stream);
+
 /* getAbsoluteCoordinates (monkeydetector.py:356-360) of a pose output: pose [n][joints * 3] float32
  * normalised by cube_z / 2 (the regressors' output), coms [n][3] float64 (u, v, d).  Per joint:
  * xyz = pose * f32(cube_z / 2) + f32(uvdtoxyz(com)) in mm, uvd = xyztouvd(xyz) (a joint with z == 0

@@ -10,8 +10,11 @@ The directory name carries a hyphen, so import it with ``importlib.import_module
 * ``train_dense_hier_networks.dense_hier_model_struct`` -- the dense-hierarchical hybrid, recorded
   as a layer graph (``_graph``) and run by the native graph runtime (``mp_graph_*``)
 * ``train_cnn_networks_hgru`` -- ``attn_model_struct`` (the attention CoM regressor),
-  ``prepare_data_test`` (device batch crop) and ``FramePosePipeline`` (frame -> CoM -> crop -> pose)
-* ``monkeydetector`` -- ``MonkeyDetector`` / ``tfMonkeyDetector``: CoM, crop (native), joint transforms
+  ``prepare_data_test`` (device batch crop), ``FramePosePipeline`` (frame -> CoM -> crop -> pose),
+  ``RealDataPipeline`` / ``eval_model_on_real_data`` (recorded camera frames as stored -> joints)
+* ``monkeydetector`` -- ``MonkeyDetector`` / ``tfMonkeyDetector``: CoM, crop (native), joint transforms;
+  ``preprocess_real_frames`` (transpose, depth gate, / max depth of recorded frames: numpy on the
+  host, ``mp_real_frames_dev`` on the device, the same bits)
 * ``pose_evaluation`` -- the pose metrics (``getMeanError_np`` ...) on numpy arrays and on CUDA tensors,
   ``PoseEvaluator`` (a streaming evaluator in device memory)
 * ``weights``     -- TF variable-name tables and deterministic synthetic initialisers

@@ -514,6 +514,35 @@ int mp_crop3d_dev_coms_dt(const mp_camera* cam, const void* frames, int depth_dt
   });
 }
 
+// ---- recorded camera frames -> the attention net's input (k_real.hip) ----------------------------
+int mp_real_frames_dev(const void* raw, int depth_dtype, int64_t n, int64_t h, int64_t w, int transposed, int gate,
+                       double lo, double hi, double fill, double max_depth, float* out, void* stream) {
+  return guard([&] {
+    if (!raw || !out) fail(MP_ERR_ARG, "mp_real_frames_dev: null pointer");
+    if (depth_dtype != MP_DEPTH_F32 && depth_dtype != MP_DEPTH_U16)
+      fail(MP_ERR_ARG, "mp_real_frames_dev: unknown depth dtype");
+    const bool u16 = depth_dtype == MP_DEPTH_U16;
+    const int64_t lim = (int64_t)1 << 30;
+    if (n <= 0 || n > 65535 || h <= 0 || w <= 0 || h > lim || w > lim || h * w > lim)
+      fail(MP_ERR_SHAPE, "mp_real_frames_dev: bad shape");
+    if ((transposed != 0 && transposed != 1) || (gate != 0 && gate != 1))
+      fail(MP_ERR_ARG, "mp_real_frames_dev: transposed and gate are 0 or 1");
+    if (reinterpret_cast<uintptr_t>(raw) & (u16 ? 1 : 3))
+      fail(MP_ERR_ARG, "mp_real_frames_dev: raw must be aligned to its element size");
+    if (reinterpret_cast<uintptr_t>(out) & 3) fail(MP_ERR_ARG, "mp_real_frames_dev: out must be 4-byte aligned");
+    if (gate && u16) {
+      for (double v : {lo, hi, fill})
+        if (!(v >= 0.0 && v <= 65535.0 && v == std::floor(v)))
+          fail(MP_ERR_ARG, "mp_real_frames_dev: uint16 frames take integer lo, hi and fill in [0, 65535]");
+    }
+    const float md = (float)max_depth;
+    if (!(md != 0.f) || std::isnan(md)) fail(MP_ERR_ARG, "mp_real_frames_dev: max_depth must be a non-zero number");
+    hip_check(mp::launch_real_frames(raw, u16, n, (int)h, (int)w, transposed != 0, gate != 0, lo, hi, fill, max_depth,
+                                     out, static_cast<hipStream_t>(stream)),
+              "real_frames");
+  });
+}
+
 int mp_abs_joints_dev(const mp_camera* cam, const float* pose, int64_t n, int64_t joints, const double* coms,
                       float* xyz, float* uvd, void* stream) {
   return guard([&] {

@@ -165,6 +165,9 @@ hipError_t launch_crop3d_coms(const mp_camera& cam, const float* frames, int N, 
 hipError_t launch_crop3d_coms_u16(const mp_camera& cam, const uint16_t* frames, int N, int H, int W,
                                   const double* coms, int dsz, float* patches, double* Ms, double* coms_out,
                                   int32_t* status, hipStream_t st, bool docom = false);
+// k_real.hip (recorded camera frames -> the attention net's input: transpose, gate, / max depth)
+hipError_t launch_real_frames(const void* raw, bool u16, int64_t n, int H, int W, bool transposed, bool gate,
+                              double lo, double hi, double fill, double max_depth, float* out, hipStream_t st);
 // k_detect.hip (the detector path: full-frame calculateCoM, getAbsoluteCoordinates)
 size_t com_work_bytes(int64_t n, int64_t hw);
 size_t com_u16_work_bytes(int64_t n, int64_t hw);

@@ -64,6 +64,11 @@ _CROP_SIGS = {
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "mp_abs_joints_dev": (ctypes.c_int, [ctypes.POINTER(_Camera), ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    # recorded camera frames -> the attention net's input (k_real.hip)
+    "mp_real_frames_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                          ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                          ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p,
+                                          ctypes.c_void_p]),
     # the validation pass on the device (k_eval.hip)
     "mp_rel_labels_dev": (ctypes.c_int, [ctypes.POINTER(_Camera), ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
@@ -106,8 +111,104 @@ def _p(a: np.ndarray):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _real_gate(gate, fill, max_depth, np_dtype):
+    """(lo, hi, fill) as scalars of ``np_dtype`` (``None`` without a gate) and f32(max_depth); an
+    integer dtype takes whole numbers in its own range, since the gate runs in the frame's dtype."""
+    md = np.float32(max_depth)
+    if not (md != 0) or np.isnan(md):
+        raise ValueError(f"max_depth must be a non-zero number, got {max_depth!r}")
+    if gate is None:
+        return None, md
+    try:
+        lo, hi = gate
+    except (TypeError, ValueError):
+        raise ValueError(f"gate must be (lo, hi) or None, got {gate!r}") from None
+    dt = np.dtype(np_dtype)
+    vals = []
+    for name, v in (("gate[0]", lo), ("gate[1]", hi), ("fill", fill)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{name} must be a real number, got {v!r}")
+        if dt.kind in "ui":
+            info = np.iinfo(dt)
+            if not (float(v) == int(v) and info.min <= int(v) <= info.max):
+                raise ValueError(f"{name} must be an integer in [{info.min}, {info.max}] for {dt} frames "
+                                 f"(the gate runs in the frames' own dtype), got {v!r}")
+            vals.append(dt.type(int(v)))
+        else:
+            with np.errstate(all="ignore"):
+                vals.append(dt.type(v))
+    return tuple(vals), md
+
+
+def preprocess_real_frames(raw, transposed=True, gate=(1000, 3000), fill=10000, max_depth=10000., stream=None,
+                           out=None):
+    """The preprocessing of ``eval_model_on_real_data`` (train_cnn_networks_hgru.py:388-392, 359) for
+    a batch of recorded frames: ``np.transpose`` of each frame as stored (``transposed``: ``raw`` is
+    [n, w, h] or a single [w, h]; else [n, h, w]), ``im[im < lo] = fill; im[im > hi] = fill`` in the
+    frames' own dtype (``gate=(lo, hi)``; ``None``: no gate), the cast to float32 (the placeholder)
+    and one float32 division by ``f32(max_depth)``.  Returns [n, h, w, 1] float32, the attention
+    net's input.
+
+    A numpy array (any real dtype) runs vectorised numpy on the host -- the CPU oracle of the
+    kernel.  A CUDA tensor, ``torch.uint16`` (the camera's own millimetres, uploaded as they are) or
+    ``torch.float32``, runs ``mp_real_frames_dev`` on the current stream (or ``stream``) into
+    ``out`` (a contiguous CUDA float32 tensor of n * h * w elements, else a new one) and returns a
+    CUDA tensor with the bits of the host function; a non-contiguous view is made contiguous first.
+    A float NaN passes the gate and +-inf is gated, as numpy's comparisons decide; a uint16 gate and
+    fill are whole numbers in [0, 65535].  Shapes, the frame limit and the argument ranges are
+    checked before any GPU call."""
+    if isinstance(raw, np.ndarray) or not hasattr(raw, "is_cuda"):
+        if stream is not None or out is not None:
+            raise ValueError("stream= and out= belong to the device path (a CUDA tensor in)")
+        a = np.asarray(raw)
+        if a.dtype.kind not in "uif":
+            raise TypeError(f"frames must have a real dtype, got {a.dtype}")
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3 or 0 in a.shape:
+            raise ValueError(f"raw must be [n, w, h] or [w, h], got {a.shape}")
+        g, md = _real_gate(gate, fill, max_depth, a.dtype)
+        im = np.transpose(a, (0, 2, 1)) if transposed else a
+        with np.errstate(all="ignore"):
+            if g is not None:
+                im = np.where((im < g[0]) | (im > g[1]), g[2], im)     # = the two masked assignments
+            return np.ascontiguousarray(im.astype(np.float32)[..., None] / md)
+    import torch
+    if raw.dim() == 2:
+        raw = raw[None]
+    if raw.dim() != 3 or 0 in raw.shape:
+        raise ValueError(f"raw must be [n, w, h] or [w, h], got {tuple(raw.shape)}")
+    n, d1, d2 = raw.shape
+    h, w = (d2, d1) if transposed else (d1, d2)
+    if n > MAX_DEV_FRAMES:
+        raise ValueError(f"at most {MAX_DEV_FRAMES} frames a call, got {n}")
+    if h * w > 1 << 30:
+        raise ValueError(f"a frame has at most 2^30 pixels, got {h} x {w}")
+    if raw.dtype not in (torch.uint16, torch.float32):
+        raise TypeError(f"CUDA frames must be torch.uint16 or torch.float32, got {raw.dtype}: convert them, or "
+                        "pass a numpy array to run the host preprocess_real_frames")
+    u16 = raw.dtype == torch.uint16
+    g, md = _real_gate(gate, fill, max_depth, np.uint16 if u16 else np.float32)
+    if not raw.is_cuda:
+        raise TypeError("raw must be a CUDA (ROCm) tensor or a numpy array")
+    if out is None:
+        out = torch.empty((n, h, w, 1), dtype=torch.float32, device=raw.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == raw.device
+              and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n * h * w):
+        raise ValueError(f"out must be a contiguous CUDA float32 tensor of {n * h * w} elements on {raw.device}")
+    r = raw.detach().contiguous()
+    st = _lib.current_stream(r.device) if stream is None else stream
+    lo, hi, fl = (0.0, 0.0, 0.0) if g is None else (float(v) for v in g)
+    _lib.check(_lib_crop().mp_real_frames_dev(ctypes.c_void_p(r.data_ptr()), DEPTH_U16 if u16 else DEPTH_F32, n, h, w,
+                                              1 if transposed else 0, 0 if g is None else 1, lo, hi, fl,
+                                              float(max_depth), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(st)))
+    return out.view(n, h, w, 1)
+
+
 class MonkeyDetector(object):
     """``MonkeyDetector`` (monkeydetector.py:21-63)."""
+
+    preprocess_real_frames = staticmethod(preprocess_real_frames)
 
     RESIZE_BILINEAR = 0
     RESIZE_CV2_NN = 1

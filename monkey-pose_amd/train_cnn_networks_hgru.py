@@ -16,6 +16,9 @@
   / ``evaluate_tfrecord``: the validation pass of ``train_model`` (160-173, 229-237) for labelled
   batches -- attention, crop + relative labels, pose, joint errors and metrics accumulated in device
   memory (``pose_evaluation.PoseEvaluator``), no host round trip.
+* ``RealDataPipeline`` / ``eval_model_on_real_data`` (342-419): recorded camera frames as stored
+  (uint16 or float32, [w, h]) -> transpose, depth gate, / image_max_depth on the device
+  (``mp_real_frames_dev``) -> the ``FramePosePipeline`` calls -> absolute joints.
 * ``cnn_model_struct().build(crops, num_classes)`` -> ``.out_put`` [N, num_classes]
   (train_cnn_networks_hgru.py:626-760): the regressor the reference's driver builds for
   validation (169), ``test_model`` (291) and ``eval_model_on_real_data`` (363) -- five conv +
@@ -341,6 +344,98 @@ class DetectorPosePipeline:
             out = self.pose.forward(patches, h2_init=h2_init)
         xyz, uvd = md.getAbsoluteCoordinates_device(out, coms, self.num_joints, out=self._out)
         return xyz, uvd, coms, Ms
+
+
+class RealDataPipeline:
+    """``eval_model_on_real_data``'s per-frame body (train_cnn_networks_hgru.py:385-407) for a batch
+    of recorded camera frames on one GPU: raw frames as stored -> transpose, gate, / image_max_depth
+    (``monkeydetector.preprocess_real_frames``, ``mp_real_frames_dev``) -> the calls of
+    ``FramePosePipeline.run`` (attention CoM, device crop, pose regressor) -> absolute joints
+    (``md.getAbsoluteCoordinates_device``).  Nothing leaves the device; the only sync is the crop
+    status read when ``check_crops`` is set.
+
+    ``run(raw, h2_init=None)``: ``raw`` CUDA [n, w, h] (``transposed``, as the recordings are stored;
+    else [n, h, w]), ``torch.uint16`` (the camera's millimetres, uploaded as they are) or
+    ``torch.float32`` -> (xyz [n, J, 3] mm, uvd [n, J, 3], coms [n, 3] f64, Ms [n, 3, 3] f64,
+    com_norm [n, 3] the attention output).  The frame buffer and xyz / uvd are reused by the next call
+    of the same batch shape and dtype.  Any ``n``: the reference runs one frame per step, and a frame's
+    results here do not depend on the batch it is in.
+
+    The crop input.  The reference crops from float64, ``(im / 10000.) * 10000.`` (399, 68); here the
+    crop reads the float32 normalised frame times ``frame_scale = image_max_depth`` in float32, like
+    ``FramePosePipeline``.  For gated uint16 frames (``oracle.crop_ref.synth_frame`` seeds 0..9, a CoM
+    over the body pixels rounded through float32) both routes give equal float32 patches and ``M``
+    (tests/test_real_frames_cpu.py): ``f32(v / 10000) * 10000`` differs from ``v`` for 9152 of the
+    65536 uint16 values, but the final ``/ 10000`` lands on the same float32.  The routes can differ
+    only where ``zstart`` or ``zend`` of a crop falls within a float32 ulp of a pixel value; nothing
+    more is claimed."""
+
+    def __init__(self, attn: attn_model_struct, pose_model, md, config: Optional[InferenceConfig] = None,
+                 gate=(1000, 3000), fill=10000, transposed: bool = True, check_crops: bool = True):
+        self.config = config or InferenceConfig()
+        self.md = md
+        self.gate, self.fill, self.transposed = gate, fill, bool(transposed)
+        self.frame_pipeline = FramePosePipeline(attn, pose_model, md, self.config, check_crops)
+        self._key, self._frames, self._out = None, None, None
+
+    def run(self, raw, h2_init=None):
+        import torch
+        from .monkeydetector import preprocess_real_frames
+        cfg = self.config
+        if not isinstance(raw, torch.Tensor):
+            raise TypeError("raw must be a CUDA (ROCm) tensor")
+        key = (tuple(raw.shape), raw.dtype, raw.device)
+        # shape, dtype, gate and device are checked in there, before any GPU call
+        frames = preprocess_real_frames(raw, self.transposed, self.gate, self.fill, cfg.image_max_depth,
+                                        out=self._frames if key == self._key else None)
+        if key != self._key:
+            n = frames.shape[0]
+            self._frames = frames
+            self._out = tuple(torch.empty((n, cfg.num_joints, 3), dtype=torch.float32, device=frames.device)
+                              for _ in range(2))
+            self._key = key
+        out, coms, Ms = self.frame_pipeline.run(frames, h2_init)
+        xyz, uvd = self.md.getAbsoluteCoordinates_device(out, coms, cfg.num_joints, out=self._out)
+        return xyz, uvd, coms, Ms, self.frame_pipeline.attn.out_put
+
+
+def eval_model_on_real_data(real_data_dir, pipeline, batch_size=16, device=None):
+    """``eval_model_on_real_data`` (train_cnn_networks_hgru.py:342-419) over a directory of recorded
+    frames: the files ``sorted(glob(real_data_dir + '*.npy'))`` (the reference's pattern: the directory
+    ends in its separator), each loaded on the host, stacked ``batch_size`` at a time, uploaded as they
+    are (uint16 stays uint16) and run through ``pipeline.run`` (a ``RealDataPipeline``).  Returns
+    (files, xyz [N, J, 3] mm, uvd [N, J, 3], coms [N, 3] f64) as numpy arrays in file order.  The last,
+    partial batch is run too: every file is a result.  All frames of a directory share one shape and
+    one dtype, ``uint16`` or ``float32``; anything else raises.  The reference's plots are out of
+    scope."""
+    import glob
+    import torch
+    files = sorted(glob.glob(real_data_dir + '*.npy'))
+    if not files:
+        raise ValueError(f"no .npy frames match {real_data_dir + '*.npy'!r}")
+    batch_size = int(batch_size)
+    if batch_size <= 0:
+        raise ValueError(f"batch_size must be positive, got {batch_size}")
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    first = None
+    for f in files:                              # the headers alone, before any frame is run
+        a = np.load(f, mmap_mode="r", allow_pickle=False)
+        if first is None:
+            if a.ndim != 2 or a.dtype not in (np.uint16, np.float32):
+                raise ValueError(f"{f}: expected a 2-D uint16 or float32 frame, got {a.dtype} {a.shape} "
+                                 "(run other dtypes through the host preprocess_real_frames)")
+            first = (a.shape, a.dtype)
+        elif (a.shape, a.dtype) != first:
+            raise ValueError(f"{f}: frame is {a.dtype} {a.shape}, but {files[0]} is {first[1]} {first[0]}; "
+                             "all frames of a directory must share one shape and dtype")
+        del a
+    xyz, uvd, coms = [], [], []
+    for i in range(0, len(files), batch_size):
+        batch = np.stack([np.load(f, allow_pickle=False) for f in files[i:i + batch_size]])
+        res = pipeline.run(torch.from_numpy(batch).to(dev))
+        for acc, t in zip((xyz, uvd, coms), res[:3]):
+            acc.append(t.detach().cpu().numpy().copy())     # a copy: the pipeline reuses its buffers
+    return files, np.concatenate(xyz), np.concatenate(uvd), np.concatenate(coms)
 
 
 class StreamPosePipeline:
