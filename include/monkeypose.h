@@ -464,6 +464,52 @@ int mp_graph_set(mp_ctx* ctx, const mp_graph_op* ops, int n_ops, int in_channels
  * tensor i densely ([n, cout] for an fc output, [n, H, W, C] otherwise) */
 int mp_graph_fwd(mp_ctx* ctx, const float* x, int64_t n, int64_t h, int64_t w, float* const* outs, void* stream);
 
+/* ---- joint overlays on the device (added after 0.3; mp_version() is unchanged) ---------------
+ * The picture the reference's inference entries end with (plt.imshow(frame); plt.scatter(uvd);
+ * save_result_image's labels / results / skeleton lines): n depth frames through a colour map with
+ * joint markers and bones drawn on them, in one asynchronous pass on `stream`.  Nothing is allocated
+ * or synchronised; every argument is validated before the launch.  The rule is
+ * csrc/overlay_geom.hpp; in short:
+ *   frames      [n][h][w] float32 (MP_DEPTH_F32) or uint16 (MP_DEPTH_U16), device memory aligned to
+ *               the element size; n <= 65535, h, w <= 4096
+ *   lo, hi      depth colour: x = (d - lo) / (hi - lo) in float32 (one IEEE division), index 0 if
+ *               !(x >= 0) (also NaN), 255 if x >= 1, else (int)(x * 255 + 0.5); finite, hi != lo
+ *               (lo > hi inverts the map)
+ *   lut         [256][3] uint8 RGB in device memory, any alignment
+ *   joints_uvd  [n][S][J][3] float32 in device memory (u, v read; d ignored), 1 <= S <= 4,
+ *               0 <= J <= 128.  Centre = floor(u + 0.5), floor(v + 0.5); a joint whose centre is
+ *               outside [-4096, 8191] (NaN, +-inf too) is not drawn and draws no bone
+ *   bones       [nb][2] int32 indices into 0..J-1 in HOST memory (read at the call), 0 <= nb <= 256,
+ *               shared by all sets and frames; NULL with nb = 0
+ *   style       per set: marker colour and radius 0..15 (0: one pixel; covered iff dx^2 + dy^2 <= r^2),
+ *               bone colour and thickness 1..15 (covered iff the pixel projects onto the segment and
+ *               4 cross^2 <= th^2 |PQ|^2, in int64; the caps are the markers').  struct_size =
+ *               sizeof(mp_overlay_style), checked
+ *   out         [n][h][w][3] uint8 RGB in device memory at any byte address
+ * A pixel takes the LAST primitive covering it in the order: for each set, its bones in list order,
+ * then its joints in index order; else the depth colour.  No blending, text or anti-aliasing.
+ * MP_ERR_SHAPE: n, h, w, S, J or nb out of range; MP_ERR_ARG: everything else. */
+typedef struct {
+  uint8_t marker_rgb[3];
+  uint8_t radius;
+  uint8_t bone_rgb[3];
+  uint8_t thickness;
+} mp_overlay_set_style;
+typedef struct {
+  uint64_t struct_size;          /* sizeof(mp_overlay_style) as the caller was compiled */
+  mp_overlay_set_style sets[4];  /* the first S are read */
+} mp_overlay_style;
+int mp_overlay_dev(const void* frames, int depth_dtype, int64_t n, int64_t h, int64_t w, float lo, float hi,
+                   const uint8_t* lut, const float* joints_uvd, int64_t S, int64_t J, const int32_t* bones, int64_t nb,
+                   const mp_overlay_style* style, uint8_t* out, void* stream);
+
+/* The uvd half of getRelativeCoordinates (monkeydetector.py:341-354) for a batch, i.e. joints in the
+ * crop's pixel space (what save_result_image draws on the patch): joints_uvd [n][joints][3] float32,
+ * Ms [n][9] float64 (the crops' transforms), device memory.  Per joint, in float64 and not fused:
+ * t_i = (u * M_i0 + v * M_i1) + M_i2; out = (f32(t_0 / t_2), f32(t_1 / t_2), d).  Asynchronous. */
+int mp_transform_joints_dev(const float* joints_uvd, const double* Ms, int64_t n, int64_t joints, float* out,
+                            void* stream);
+
 /* ---- HBM streaming probe (diagnostic; bench.py's practical roof) ----------------------------
  * The box's streaming HBM rates over `bytes`-sized buffers (>= 64 MiB; 2 GiB recommended):
  * read-only, write-only and copy (read + write bytes / time), each the best over grids of 1024 -

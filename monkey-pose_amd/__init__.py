@@ -14,7 +14,9 @@ The directory name carries a hyphen, so import it with ``importlib.import_module
   ``RealDataPipeline`` / ``eval_model_on_real_data`` (recorded camera frames as stored -> joints)
 * ``monkeydetector`` -- ``MonkeyDetector`` / ``tfMonkeyDetector``: CoM, crop (native), joint transforms;
   ``preprocess_real_frames`` (transpose, depth gate, / max depth of recorded frames: numpy on the
-  host, ``mp_real_frames_dev`` on the device, the same bits)
+  host, ``mp_real_frames_dev`` on the device, the same bits); ``render_overlays`` (depth frames
+  through a colour table with joint markers and bones drawn on them: ``mp_overlay_dev``) and
+  ``render_overlays_np`` (the same rule in numpy)
 * ``pose_evaluation`` -- the pose metrics (``getMeanError_np`` ...) on numpy arrays and on CUDA tensors,
   ``PoseEvaluator`` (a streaming evaluator in device memory)
 * ``weights``     -- TF variable-name tables and deterministic synthetic initialisers

@@ -69,6 +69,13 @@ _CROP_SIGS = {
                                           ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                           ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p,
                                           ctypes.c_void_p]),
+    # joint overlays and crop-space joints (k_overlay.hip)
+    "mp_overlay_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                      ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "mp_transform_joints_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                               ctypes.c_void_p, ctypes.c_void_p]),
     # the validation pass on the device (k_eval.hip)
     "mp_rel_labels_dev": (ctypes.c_int, [ctypes.POINTER(_Camera), ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
@@ -205,10 +212,276 @@ def preprocess_real_frames(raw, transposed=True, gate=(1000, 3000), fill=10000, 
     return out.view(n, h, w, 1)
 
 
+# ---------------------------------------------------------------------- joint overlays
+# The drawing rule is csrc/overlay_geom.hpp (the kernel's text); render_overlays_np states it in numpy.
+OVERLAY_MAX_HW, OVERLAY_MAX_SETS, OVERLAY_MAX_JOINTS, OVERLAY_MAX_BONES = 4096, 4, 128, 256
+OVERLAY_MAX_RADIUS, OVERLAY_MAX_THICK = 15, 15
+OVERLAY_C_MIN, OVERLAY_C_MAX = -4096, 8191
+
+# per set (marker RGB, bone RGB, marker radius, bone thickness): set 0 (e.g. labels) green, set 1
+# (e.g. results) red, then blue and yellow
+DEFAULT_OVERLAY_STYLES = (((0, 255, 0), (0, 160, 0), 3, 1), ((255, 0, 0), (200, 0, 0), 3, 1),
+                          ((0, 128, 255), (0, 96, 200), 3, 1), ((255, 255, 0), (200, 200, 0), 3, 1))
+
+
+class _OverlaySetStyle(ctypes.Structure):
+    _fields_ = [("marker_rgb", ctypes.c_uint8 * 3), ("radius", ctypes.c_uint8),
+                ("bone_rgb", ctypes.c_uint8 * 3), ("thickness", ctypes.c_uint8)]
+
+
+class OverlayStyle(ctypes.Structure):
+    """``mp_overlay_style`` (include/monkeypose.h)."""
+    _fields_ = [("struct_size", ctypes.c_uint64), ("sets", _OverlaySetStyle * 4)]
+
+
+def overlay_lut(name="gray"):
+    """The [256, 3] uint8 colour table ``name``.  ``'gray'``: entry k is (k, k, k).  ``'jet'``: the
+    piecewise-linear blue - cyan - yellow - red map, with x = k / 255 in float64:
+    ``r = clip(1.5 - |4x - 3|, 0, 1)``, ``g = clip(1.5 - |4x - 2|, 0, 1)``,
+    ``b = clip(1.5 - |4x - 1|, 0, 1)``, each stored as ``rint(255 c)``."""
+    k = np.arange(256)
+    if name == "gray":
+        return np.repeat(k.astype(np.uint8)[:, None], 3, axis=1)
+    if name == "jet":
+        x = k / 255.0
+        rgb = [np.clip(1.5 - np.abs(4.0 * x - c), 0.0, 1.0) for c in (3.0, 2.0, 1.0)]
+        return np.rint(255.0 * np.stack(rgb, axis=1)).astype(np.uint8)
+    raise ValueError(f"unknown colour table {name!r}: 'gray' or 'jet'")
+
+
+def _overlay_lut_array(lut):
+    if isinstance(lut, str):
+        return overlay_lut(lut)
+    a = np.asarray(lut)
+    if a.dtype != np.uint8 or a.shape != (256, 3):
+        raise ValueError(f"lut must be a name or a [256, 3] uint8 table, got {a.dtype} {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def _overlay_scene(n, h, w, jshape, bones, depth_range, styles):
+    """The checks shared by ``render_overlays`` and ``render_overlays_np``, all before any GPU call ->
+    (S, J, bones [nb, 2] int32, f32 lo, f32 hi, styles as S tuples)."""
+    if n <= 0 or h <= 0 or w <= 0:
+        raise ValueError(f"frames must be a non-empty [n, h, w], got {(n, h, w)}")
+    if h > OVERLAY_MAX_HW or w > OVERLAY_MAX_HW:
+        raise ValueError(f"h and w are at most {OVERLAY_MAX_HW}, got {h} x {w}")
+    if n > MAX_DEV_FRAMES:
+        raise ValueError(f"at most {MAX_DEV_FRAMES} frames a call, got {n}")
+    jshape = tuple(jshape)
+    if len(jshape) == 3:
+        jshape = (jshape[0], 1) + jshape[1:]
+    if len(jshape) != 4 or jshape[0] != n or jshape[3] != 3:
+        raise ValueError(f"joints_uvd must be [{n}, S, J, 3] or [{n}, J, 3], got {jshape}")
+    S, J = jshape[1], jshape[2]
+    if not 1 <= S <= OVERLAY_MAX_SETS:
+        raise ValueError(f"1 to {OVERLAY_MAX_SETS} joint sets, got {S}")
+    if J > OVERLAY_MAX_JOINTS:
+        raise ValueError(f"at most {OVERLAY_MAX_JOINTS} joints a set, got {J}")
+    if bones is None:
+        b = np.zeros((0, 2), np.int32)
+    else:
+        b = np.asarray(bones)
+        if b.size == 0:
+            b = np.zeros((0, 2), np.int32)
+        if b.dtype.kind not in "ui" or b.ndim != 2 or b.shape[1] != 2:
+            raise ValueError(f"bones must be [nb, 2] integer index pairs, got {b.dtype} {b.shape}")
+        if len(b) > OVERLAY_MAX_BONES:
+            raise ValueError(f"at most {OVERLAY_MAX_BONES} bones, got {len(b)}")
+        if len(b) and (b.min() < 0 or b.max() >= J):
+            raise ValueError(f"a bone index is outside 0..{J - 1}")
+        b = np.ascontiguousarray(b, dtype=np.int32)
+    try:
+        lo, hi = depth_range
+        with np.errstate(all="ignore"):
+            lo, hi = np.float32(lo), np.float32(hi)
+    except (TypeError, ValueError):
+        raise ValueError(f"depth_range must be (lo, hi), got {depth_range!r}") from None
+    if not (np.isfinite(lo) and np.isfinite(hi)) or lo == hi:
+        raise ValueError(f"depth_range must be two finite float32 values that differ, got {depth_range!r}")
+    st = DEFAULT_OVERLAY_STYLES if styles is None else tuple(styles)
+    if len(st) < S:
+        raise ValueError(f"{S} joint sets need {S} styles, got {len(st)}")
+    out = []
+    for s in st[:S]:
+        try:
+            m, c, r, th = s
+            m, c = tuple(int(v) for v in m), tuple(int(v) for v in c)
+            r, th = int(r), int(th)
+        except (TypeError, ValueError):
+            raise ValueError(f"a style is (marker_rgb, bone_rgb, radius, thickness), got {s!r}") from None
+        if len(m) != 3 or len(c) != 3 or not all(0 <= v <= 255 for v in m + c):
+            raise ValueError(f"style colours are three values in 0..255, got {s!r}")
+        if not 0 <= r <= OVERLAY_MAX_RADIUS or not 1 <= th <= OVERLAY_MAX_THICK:
+            raise ValueError(f"radius is 0..{OVERLAY_MAX_RADIUS} and thickness 1..{OVERLAY_MAX_THICK}, got {s!r}")
+        out.append((m, c, r, th))
+    return S, J, b, lo, hi, out
+
+
+def overlay_color_index(d, lo, hi):
+    """The colour-table index of frame values ``d`` (float32 array): ``x = (d - lo) / (hi - lo)`` in
+    float32, 0 if ``not x >= 0`` (also NaN), 255 if ``x >= 1``, else ``int(x * 255 + 0.5)``."""
+    f32 = np.float32
+    with np.errstate(all="ignore"):
+        x = (np.asarray(d, f32) - f32(lo)) / (f32(hi) - f32(lo))
+        mid = (x >= 0) & ~(x >= 1)
+        k = np.zeros(x.shape, np.int64)
+        k[x >= 1] = 255
+        k[mid] = (x[mid] * f32(255.) + f32(0.5)).astype(np.int64)
+    return k
+
+
+def overlay_centers(uv):
+    """(eligible, centres int64) of joint coordinates ``uv`` [..., 2] float32: ``floor(u + 0.5)`` in
+    float32; eligible iff both centres are in [-4096, 8191] (NaN and +-inf are not)."""
+    with np.errstate(all="ignore"):
+        f = np.floor(np.asarray(uv, np.float32) + np.float32(0.5))
+        ok = ((f >= OVERLAY_C_MIN) & (f <= OVERLAY_C_MAX)).all(axis=-1)
+        c = np.where(ok[..., None], f, 0).astype(np.int64)
+    return ok, c
+
+
+def overlay_disc_mask(X, Y, cu, cv, r):
+    return (X - cu) ** 2 + (Y - cv) ** 2 <= r * r
+
+
+def overlay_bone_mask(X, Y, P, Q, th):
+    """int64 coverage of the bone P -> Q, ``th`` thick, at pixel grids X, Y (the caps are the markers')"""
+    dx, dy = int(Q[0]) - int(P[0]), int(Q[1]) - int(P[1])
+    L2 = dx * dx + dy * dy
+    ex, ey = X.astype(np.int64) - int(P[0]), Y.astype(np.int64) - int(P[1])
+    s = ex * dx + ey * dy
+    c = ex * dy - ey * dx
+    return (L2 > 0) & (0 <= s) & (s <= L2) & (4 * c * c <= th * th * L2)
+
+
+def render_overlays_np(frames, joints_uvd, bones=None, depth_range=None, lut="gray", styles=None):
+    """``render_overlays`` in numpy on host arrays -- the statement of the drawing rule the kernel is
+    tested against (float32 colour arithmetic, int64 coverage, vectorised per primitive over its
+    bounding box).  Returns [n, h, w, 3] uint8."""
+    fr = np.asarray(frames)
+    if fr.ndim == 4 and fr.shape[-1] == 1:
+        fr = fr[..., 0]
+    if fr.ndim != 3:
+        raise ValueError(f"frames must be [n, h, w] or [n, h, w, 1], got {fr.shape}")
+    if fr.dtype not in (np.uint16, np.float32):
+        raise TypeError(f"frames must be uint16 or float32, got {fr.dtype}")
+    n, h, w = fr.shape
+    ju = np.asarray(joints_uvd)
+    if ju.dtype != np.float32:
+        raise TypeError(f"joints_uvd must be float32, got {ju.dtype}")
+    if depth_range is None:
+        depth_range = (0, 10000) if fr.dtype == np.uint16 else (0.0, 1.0)
+    S, J, b, lo, hi, st = _overlay_scene(n, h, w, ju.shape, bones, depth_range, styles)
+    table = _overlay_lut_array(lut)
+    ju = ju.reshape(n, S, J, 3)
+    out = table[overlay_color_index(fr.astype(np.float32), lo, hi)]
+    ok, cen = overlay_centers(ju[..., :2])
+
+    def paint(img, x0, x1, y0, y1, mask_of, rgb):
+        x0, x1, y0, y1 = max(x0, 0), min(x1, w - 1), max(y0, 0), min(y1, h - 1)
+        if x0 > x1 or y0 > y1:
+            return
+        Y, X = np.mgrid[y0:y1 + 1, x0:x1 + 1]
+        img[y0:y1 + 1, x0:x1 + 1][mask_of(X, Y)] = rgb
+
+    for i in range(n):
+        for s in range(S):
+            m_rgb, b_rgb, r, th = st[s]
+            for a, q in b:
+                if ok[i, s, a] and ok[i, s, q]:
+                    P, Q = cen[i, s, a], cen[i, s, q]
+                    paint(out[i], min(P[0], Q[0]) - th, max(P[0], Q[0]) + th, min(P[1], Q[1]) - th,
+                          max(P[1], Q[1]) + th, lambda X, Y: overlay_bone_mask(X, Y, P, Q, th), b_rgb)
+            for j in range(J):
+                if ok[i, s, j]:
+                    cu, cv = cen[i, s, j]
+                    paint(out[i], cu - r, cu + r, cv - r, cv + r,
+                          lambda X, Y: overlay_disc_mask(X, Y, cu, cv, r), m_rgb)
+    return out
+
+
+_LUT_CACHE = {}
+
+
+def render_overlays(frames, joints_uvd, bones=None, depth_range=None, lut="gray", styles=None, stream=None,
+                    out=None):
+    """Depth frames through a colour table with joint markers and bones drawn on them, on the device
+    (``mp_overlay_dev``, one streaming kernel on the current stream or ``stream``): what the
+    reference's ``plt.imshow(frame); plt.scatter(uvd)`` and ``save_result_image`` show.
+
+    frames       CUDA [n, h, w] or [n, h, w, 1], ``torch.uint16`` or ``torch.float32``; h, w <= 4096
+    joints_uvd   CUDA float32 [n, S, J, 3] or [n, J, 3] (one set); u, v are read.  1 <= S <= 4,
+                 J <= 128.  A joint whose rounded centre is outside [-4096, 8191] (NaN too) is not
+                 drawn and draws no bone: pad a short set with NaN
+    bones        [nb, 2] index pairs into 0..J-1 (host), nb <= 256; ``None``: markers only
+    depth_range  (lo, hi) of the colour table in the frames' units, as float32; default (0, 10000)
+                 for uint16 frames and (0, 1) for float32 frames
+    lut          ``'gray'``, ``'jet'`` (``overlay_lut``), a [256, 3] uint8 array or CUDA tensor
+    styles       per set (marker_rgb, bone_rgb, radius 0..15, thickness 1..15);
+                 ``DEFAULT_OVERLAY_STYLES``
+    out          a contiguous CUDA uint8 tensor of n * h * w * 3 elements at any byte offset
+    Returns CUDA uint8 [n, h, w, 3], the bytes of ``render_overlays_np``.  Set s + 1 is drawn over set
+    s, joints over bones, the last primitive wins; no blending, text or anti-aliasing.  Everything is
+    checked before any GPU call."""
+    import torch
+    if not isinstance(frames, torch.Tensor) or not isinstance(joints_uvd, torch.Tensor):
+        raise TypeError("frames and joints_uvd must be CUDA (ROCm) tensors (numpy: render_overlays_np)")
+    if frames.dim() == 4 and frames.shape[-1] == 1:
+        frames = frames[..., 0]
+    if frames.dim() != 3:
+        raise ValueError(f"frames must be [n, h, w] or [n, h, w, 1], got {tuple(frames.shape)}")
+    if frames.dtype not in (torch.uint16, torch.float32):
+        raise TypeError(f"frames must be torch.uint16 or torch.float32, got {frames.dtype}")
+    if joints_uvd.dtype != torch.float32:
+        raise TypeError(f"joints_uvd must be torch.float32, got {joints_uvd.dtype}")
+    u16 = frames.dtype == torch.uint16
+    n, h, w = frames.shape
+    if depth_range is None:
+        depth_range = (0, 10000) if u16 else (0.0, 1.0)
+    S, J, b, lo, hi, st = _overlay_scene(n, h, w, joints_uvd.shape, bones, depth_range, styles)
+    if isinstance(lut, torch.Tensor):
+        if lut.dtype != torch.uint8 or tuple(lut.shape) != (256, 3):
+            raise ValueError(f"lut must be [256, 3] uint8, got {lut.dtype} {tuple(lut.shape)}")
+        table = None
+    else:
+        table = _overlay_lut_array(lut)
+    if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and out.is_contiguous()
+                                and out.numel() == n * h * w * 3):
+        raise ValueError(f"out must be a contiguous CUDA uint8 tensor of {n * h * w * 3} elements")
+    if not (frames.is_cuda and joints_uvd.is_cuda and (out is None or out.is_cuda)
+            and (table is not None or lut.is_cuda)):
+        raise TypeError("frames, joints_uvd (and out, lut) must be CUDA (ROCm) tensors")
+    dev = frames.device
+    if table is not None:
+        key = (table.tobytes(), dev)
+        lut = _LUT_CACHE.get(key)
+        if lut is None:
+            lut = _LUT_CACHE[key] = torch.from_numpy(table).to(dev)
+    style = OverlayStyle(struct_size=ctypes.sizeof(OverlayStyle))
+    for s, (m, c, r, th) in enumerate(st):
+        style.sets[s].marker_rgb[:] = m
+        style.sets[s].bone_rgb[:] = c
+        style.sets[s].radius, style.sets[s].thickness = r, th
+    fr = frames.detach().contiguous()
+    ju = joints_uvd.detach().contiguous()
+    lt = lut.detach().contiguous()
+    if out is None:
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+    stp = _lib.current_stream(dev) if stream is None else stream
+    _lib.check(_lib_crop().mp_overlay_dev(ctypes.c_void_p(fr.data_ptr()), DEPTH_U16 if u16 else DEPTH_F32, n, h, w,
+                                          float(lo), float(hi), ctypes.c_void_p(lt.data_ptr()),
+                                          ctypes.c_void_p(ju.data_ptr() if J else None), S, J,
+                                          _p(b) if len(b) else None, len(b), ctypes.byref(style),
+                                          ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stp)))
+    return out.view(n, h, w, 3)
+
+
 class MonkeyDetector(object):
     """``MonkeyDetector`` (monkeydetector.py:21-63)."""
 
     preprocess_real_frames = staticmethod(preprocess_real_frames)
+    render_overlays = staticmethod(render_overlays)
+    render_overlays_np = staticmethod(render_overlays_np)
 
     RESIZE_BILINEAR = 0
     RESIZE_CV2_NN = 1
@@ -486,6 +759,36 @@ class MonkeyDetector(object):
                                                  ctypes.c_void_p(c.data_ptr()), ctypes.c_void_p(xyz.data_ptr()),
                                                  ctypes.c_void_p(uvd.data_ptr()), ctypes.c_void_p(st)))
         return xyz, uvd
+
+    def transform_joints_device(self, joints_uvd, Ms, stream=None, out=None):
+        """The uvd half of ``getRelativeCoordinates`` (monkeydetector.py:341-354) for a batch on the
+        GPU (``mp_transform_joints_dev``): joints in the crop's pixel space, which is what
+        ``save_result_image`` draws on the 128 x 128 patch.  ``joints_uvd`` CUDA [n, J, 3] fp32,
+        ``Ms`` CUDA [n, 3, 3] f64 (the crops' transforms) -> CUDA [n, J, 3] fp32.  Per joint, in
+        float64 and not fused: ``t_i = (u * M_i0 + v * M_i1) + M_i2``, ``u' = f32(t_0 / t_2)``,
+        ``v' = f32(t_1 / t_2)``, ``d' = d``.  The host function forms ``t`` by a BLAS product, which
+        may fuse or reorder, so the two can differ in the last float32 bit."""
+        import torch
+        if not isinstance(joints_uvd, torch.Tensor) or not isinstance(Ms, torch.Tensor):
+            raise TypeError("joints_uvd and Ms must be CUDA (ROCm) tensors")
+        if joints_uvd.dim() != 3 or joints_uvd.shape[2] != 3 or 0 in joints_uvd.shape:
+            raise ValueError(f"joints_uvd must be [n, joints, 3], got {tuple(joints_uvd.shape)}")
+        n, J = joints_uvd.shape[0], joints_uvd.shape[1]
+        if tuple(Ms.shape) != (n, 3, 3):
+            raise ValueError(f"Ms must be [{n}, 3, 3], got {tuple(Ms.shape)}")
+        if not (joints_uvd.is_cuda and Ms.is_cuda):
+            raise TypeError("joints_uvd and Ms must be CUDA (ROCm) tensors")
+        ju = joints_uvd.detach().float().contiguous()
+        m = Ms.detach().double().contiguous()
+        if out is None:
+            out = torch.empty((n, J, 3), dtype=torch.float32, device=ju.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32
+                  and out.is_contiguous() and out.numel() == n * J * 3):
+            raise ValueError(f"out must be a contiguous CUDA float32 tensor of {n * J * 3} elements")
+        st = _lib.current_stream(ju.device) if stream is None else stream
+        _lib.check(_lib_crop().mp_transform_joints_dev(ctypes.c_void_p(ju.data_ptr()), ctypes.c_void_p(m.data_ptr()),
+                                                       n, J, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(st)))
+        return out.view(n, J, 3)
 
     # ------------------------------------------------------------------ labels (validation pass)
     @staticmethod

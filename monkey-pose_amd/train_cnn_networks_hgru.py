@@ -18,7 +18,9 @@
   memory (``pose_evaluation.PoseEvaluator``), no host round trip.
 * ``RealDataPipeline`` / ``eval_model_on_real_data`` (342-419): recorded camera frames as stored
   (uint16 or float32, [w, h]) -> transpose, depth gate, / image_max_depth on the device
-  (``mp_real_frames_dev``) -> the ``FramePosePipeline`` calls -> absolute joints.
+  (``mp_real_frames_dev``) -> the ``FramePosePipeline`` calls -> absolute joints.  The pipelines'
+  ``render`` draws the joints on the frames on the device (``monkeydetector.render_overlays``): the
+  picture the reference's loops end with.
 * ``cnn_model_struct().build(crops, num_classes)`` -> ``.out_put`` [N, num_classes]
   (train_cnn_networks_hgru.py:626-760): the regressor the reference's driver builds for
   validation (169), ``test_model`` (291) and ``eval_model_on_real_data`` (363) -- five conv +
@@ -212,9 +214,11 @@ class FramePosePipeline:
         self.attn, self.pose, self.md = attn, pose_model, md
         self.config = config or InferenceConfig()
         self.check_crops = check_crops
+        self._last_frames = None
 
     def run(self, frames, h2_init=None):
         cfg = self.config
+        self._last_frames = frames
         com_norm = self.attn.build(frames, cfg.num_dims)
         patches, Ms, coms = self.md.crop_batch_device(
             frames, com_norm, com_scale=(cfg.image_orig_size[0], cfg.image_orig_size[1], cfg.image_max_depth),
@@ -222,6 +226,15 @@ class FramePosePipeline:
         kw = {} if h2_init is None else {"h2_init": h2_init}    # cnn_model_struct has no hidden state
         out = self.pose.build(patches, cfg.num_classes, **kw)
         return out, coms, Ms
+
+    def render(self, joints_uvd, **kw):
+        """The frames of the last ``run`` with ``joints_uvd`` (CUDA [n, J, 3] or [n, S, J, 3], e.g. the
+        uvd of ``md.getAbsoluteCoordinates_device``) drawn on them: ``monkeydetector.render_overlays``
+        and its keywords -> CUDA uint8 [n, h, w, 3]."""
+        from .monkeydetector import render_overlays
+        if self._last_frames is None:
+            raise RuntimeError("render() draws the frames of the last run(): call run() first")
+        return render_overlays(self._last_frames, joints_uvd, **kw)
 
 
 class ValidationPipeline:
@@ -301,6 +314,17 @@ def evaluate_tfrecord(tfrecord_file, pipeline: ValidationPipeline, batch_size, m
     return pipeline.summary()
 
 
+def _render_sets(frames, uvd, extra_sets, kw):
+    """``render_overlays`` of ``frames`` with ``uvd`` as set 0 and ``extra_sets`` drawn over it"""
+    import torch
+    from .monkeydetector import render_overlays
+    sets = [uvd] + list(extra_sets or [])
+    if any(not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(uvd.shape) for t in sets):
+        raise ValueError(f"every extra joint set must be a tensor of shape {tuple(uvd.shape)} (pad with NaN)")
+    joints = uvd if len(sets) == 1 else torch.stack([t.to(uvd.dtype) for t in sets], dim=1)
+    return render_overlays(frames, joints, **kw)
+
+
 class DetectorPosePipeline:
     """SURVEY config 5 for a batch, device-resident: ``MonkeyDetector``'s own ``calculateCoM`` of
     every frame (``mp_center_of_mass_dev_dt``) -> device crop around those float64 CoMs
@@ -322,6 +346,15 @@ class DetectorPosePipeline:
         self.dsize, self.num_joints = int(dsize), int(num_joints)
         self.docom, self.frame_scale, self.check_crops = bool(docom), float(frame_scale), bool(check_crops)
         self._key, self._buf, self._out = None, None, None
+        self._last = None
+
+    def render(self, extra_sets=None, **kw):
+        """The frames given to the last ``run`` with its uvd joints drawn on them
+        (``monkeydetector.render_overlays`` and its keywords) -> CUDA uint8 [n, h, w, 3].
+        ``extra_sets``: further CUDA [n, J, 3] joint sets drawn over them (pad a short one with NaN)."""
+        if self._last is None:
+            raise RuntimeError("render() draws the frames of the last run(): call run() first")
+        return _render_sets(self._last[0], self._last[1], extra_sets, kw)
 
     def run(self, frames, h2_init=None):
         import torch
@@ -343,6 +376,7 @@ class DetectorPosePipeline:
         else:
             out = self.pose.forward(patches, h2_init=h2_init)
         xyz, uvd = md.getAbsoluteCoordinates_device(out, coms, self.num_joints, out=self._out)
+        self._last = (fr, uvd)
         return xyz, uvd, coms, Ms
 
 
@@ -377,6 +411,7 @@ class RealDataPipeline:
         self.gate, self.fill, self.transposed = gate, fill, bool(transposed)
         self.frame_pipeline = FramePosePipeline(attn, pose_model, md, self.config, check_crops)
         self._key, self._frames, self._out = None, None, None
+        self._drawn = False
 
     def run(self, raw, h2_init=None):
         import torch
@@ -396,18 +431,37 @@ class RealDataPipeline:
             self._key = key
         out, coms, Ms = self.frame_pipeline.run(frames, h2_init)
         xyz, uvd = self.md.getAbsoluteCoordinates_device(out, coms, cfg.num_joints, out=self._out)
+        self._drawn = True
         return xyz, uvd, coms, Ms, self.frame_pipeline.attn.out_put
 
+    def render(self, bones=None, depth_range=None, extra_sets=None, **kw):
+        """The picture the reference's loop ends with (``plt.imshow(im); plt.scatter(uvd)``, 409-415),
+        on the device: the last ``run``'s frames -- the gated, normalised float32 buffer kept here --
+        with its uvd joints drawn on them (``monkeydetector.render_overlays`` and its keywords) ->
+        CUDA uint8 [n, h, w, 3].  ``depth_range`` defaults to the gate in the frames' units,
+        ``(lo, hi) / image_max_depth`` ((0, 1) without a gate).  ``extra_sets``: further CUDA
+        [n, J, 3] joint sets drawn over the results (pad a short one, such as a CoM, with NaN)."""
+        if not self._drawn:
+            raise RuntimeError("render() draws the frames of the last run(): call run() first")
+        if depth_range is None:
+            md = float(self.config.image_max_depth)
+            depth_range = (0.0, 1.0) if self.gate is None else (self.gate[0] / md, self.gate[1] / md)
+        return _render_sets(self._frames, self._out[1], extra_sets, dict(kw, bones=bones, depth_range=depth_range))
 
-def eval_model_on_real_data(real_data_dir, pipeline, batch_size=16, device=None):
+
+def eval_model_on_real_data(real_data_dir, pipeline, batch_size=16, device=None, overlay=None, overlay_args=None):
     """``eval_model_on_real_data`` (train_cnn_networks_hgru.py:342-419) over a directory of recorded
     frames: the files ``sorted(glob(real_data_dir + '*.npy'))`` (the reference's pattern: the directory
     ends in its separator), each loaded on the host, stacked ``batch_size`` at a time, uploaded as they
     are (uint16 stays uint16) and run through ``pipeline.run`` (a ``RealDataPipeline``).  Returns
     (files, xyz [N, J, 3] mm, uvd [N, J, 3], coms [N, 3] f64) as numpy arrays in file order.  The last,
     partial batch is run too: every file is a result.  All frames of a directory share one shape and
-    one dtype, ``uint16`` or ``float32``; anything else raises.  The reference's plots are out of
-    scope."""
+    one dtype, ``uint16`` or ``float32``; anything else raises.
+
+    The reference's plot of every frame (409-415) is ``overlay``: a callback called once per batch with
+    ``(files, rgb)``, the batch's file names and ``pipeline.render(**overlay_args)`` copied to the host
+    as a numpy uint8 [n, h, w, 3] array (the depth frame through a colour table, the joints drawn on
+    it).  ``None``: nothing is drawn; the four returned values are the same either way."""
     import glob
     import torch
     files = sorted(glob.glob(real_data_dir + '*.npy'))
@@ -435,6 +489,8 @@ def eval_model_on_real_data(real_data_dir, pipeline, batch_size=16, device=None)
         res = pipeline.run(torch.from_numpy(batch).to(dev))
         for acc, t in zip((xyz, uvd, coms), res[:3]):
             acc.append(t.detach().cpu().numpy().copy())     # a copy: the pipeline reuses its buffers
+        if overlay is not None:
+            overlay(files[i:i + batch_size], pipeline.render(**(overlay_args or {})).cpu().numpy())
     return files, np.concatenate(xyz), np.concatenate(uvd), np.concatenate(coms)
 
 

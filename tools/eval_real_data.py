@@ -4,7 +4,10 @@ train_cnn_networks_hgru.RealDataPipeline / eval_model_on_real_data.  Every ``*.n
 directory (uint16 or float32, stored [w, h]) is uploaded as it is, transposed, gated to
 [--gate-lo, --gate-hi] mm and normalised on the device, then attention CoM -> crop -> pose -> absolute
 joints.  Writes joints_xyz.npy [N, J, 3] (mm), joints_uvd.npy [N, J, 3], coms.npy [N, 3] and
-files.txt (one path per line, the order of the arrays' rows) into --out-dir.
+files.txt (one path per line, the order of the arrays' rows) into --out-dir.  With --overlay it also
+writes overlay_%05d.png, one picture per frame in that order: the gated depth frame through a colour
+table with the joints drawn on it on the device (RealDataPipeline.render; what the reference shows with
+plt.imshow / plt.scatter), and with --bones FILE.json (a list of joint index pairs) the skeleton lines.
 
 The models get the variables of --checkpoint DIR (a TF checkpoint holding the attention and the pose
 variables), or synthetic weights.  Without a directory it first writes --frames synthetic recordings
@@ -15,13 +18,17 @@ stops on the child's failure.
 
     python tools/eval_real_data.py [DIR] [--batch 16] [--model cnn|hgru] [--checkpoint DIR]
                                    [--out-dir real_eval] [--no-gate] [--plain]
+                                   [--overlay] [--bones FILE.json] [--lut gray|jet]
 """
 import argparse
 import importlib
+import json
 import os
+import struct
 import subprocess
 import sys
 import tempfile
+import zlib
 
 import numpy as np
 
@@ -37,6 +44,35 @@ def write_synthetic(d, frames, seed):
     for i, f in enumerate(mm):
         np.save(os.path.join(d, f"frame_{i:05d}.npy"), np.ascontiguousarray(f.T))     # stored [w, h]
     return d
+
+
+def write_png(path, rgb):
+    """An [h, w, 3] uint8 array as an 8-bit RGB PNG: IHDR, one IDAT of the zlib stream of the rows (each
+    behind filter byte 0), IEND."""
+    rgb = np.asarray(rgb)
+    if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3 or 0 in rgb.shape:
+        raise ValueError(f"expected an [h, w, 3] uint8 image, got {rgb.dtype} {rgb.shape}")
+    h, w, _ = rgb.shape
+    rows = np.zeros((h, 1 + 3 * w), np.uint8)
+    rows[:, 1:] = rgb.reshape(h, 3 * w)
+
+    def chunk(kind, body):
+        return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xffffffff)
+
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0))
+                + chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b""))
+
+
+def read_bones(path):
+    """--bones FILE.json: a list of [a, b] joint index pairs (None without a file)"""
+    if not path:
+        return None
+    with open(path) as f:
+        pairs = json.load(f)
+    if not isinstance(pairs, list) or any(not isinstance(p, list) or len(p) != 2 for p in pairs):
+        raise ValueError(f"{path}: expected a JSON list of [a, b] index pairs")
+    return [(int(a), int(b)) for a, b in pairs]
 
 
 def child(a):
@@ -58,7 +94,17 @@ def child(a):
     gate = None if a.no_gate else (a.gate_lo, a.gate_hi)
     pipe = T.RealDataPipeline(attn, pose, md, cfg, gate=gate, fill=a.fill, transposed=not a.plain,
                               check_crops=not a.no_check)
-    files, xyz, uvd, coms = T.eval_model_on_real_data(a.dir, pipe, batch_size=a.batch)
+    os.makedirs(a.out_dir, exist_ok=True)
+    drawn = []
+
+    def overlay(batch_files, rgb):
+        for img in rgb:
+            write_png(os.path.join(a.out_dir, "overlay_%05d.png" % len(drawn)), img)
+            drawn.append(1)
+
+    files, xyz, uvd, coms = T.eval_model_on_real_data(
+        a.dir, pipe, batch_size=a.batch, overlay=overlay if a.overlay else None,
+        overlay_args=dict(bones=read_bones(a.bones), lut=a.lut))
     torch.cuda.synchronize()
     os.makedirs(a.out_dir, exist_ok=True)
     np.save(os.path.join(a.out_dir, "joints_xyz.npy"), xyz)
@@ -67,7 +113,7 @@ def child(a):
     with open(os.path.join(a.out_dir, "files.txt"), "w") as f:
         f.write("".join(p + "\n" for p in files))
     print(f"RESULT {len(files)} frames -> {a.out_dir}: joints_xyz.npy {xyz.shape}, joints_uvd.npy {uvd.shape}, "
-          f"coms.npy {coms.shape}, files.txt", flush=True)
+          f"coms.npy {coms.shape}, files.txt" + (f", {len(drawn)} overlay_*.png" if a.overlay else ""), flush=True)
     return 0
 
 
@@ -84,6 +130,9 @@ def main():
     ap.add_argument("--no-gate", action="store_true", help="feed the frames ungated")
     ap.add_argument("--plain", action="store_true", help="the frames are stored [h, w] already")
     ap.add_argument("--no-check", action="store_true", help="do not read the crop status back per batch")
+    ap.add_argument("--overlay", action="store_true", help="write overlay_%%05d.png, one picture per frame")
+    ap.add_argument("--bones", help="JSON file of joint index pairs: the skeleton lines of --overlay")
+    ap.add_argument("--lut", choices=["gray", "jet"], default="gray", help="the colour table of --overlay")
     ap.add_argument("--frames", type=int, default=8, help="synthetic recordings to write when no directory is given")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
@@ -99,9 +148,11 @@ def main():
         a.dir += os.sep                          # the reference globs real_data_dir + '*.npy'
     cmd = [sys.executable, os.path.abspath(__file__), a.dir, "--child", "--batch", str(a.batch), "--model", a.model,
            "--out-dir", a.out_dir, "--gate-lo", str(a.gate_lo), "--gate-hi", str(a.gate_hi), "--fill", str(a.fill),
-           "--seed", str(a.seed)]
+           "--seed", str(a.seed), "--lut", a.lut]
+    cmd += ["--bones", a.bones] if a.bones else []
     cmd += ["--checkpoint", a.checkpoint] if a.checkpoint else []
-    for flag, on in (("--no-gate", a.no_gate), ("--plain", a.plain), ("--no-check", a.no_check)):
+    for flag, on in (("--no-gate", a.no_gate), ("--plain", a.plain), ("--no-check", a.no_check),
+                     ("--overlay", a.overlay)):
         cmd += [flag] if on else []
     try:
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=CHILD_LIMIT_S)
