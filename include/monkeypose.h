@@ -413,9 +413,50 @@ int mp_eval_summary_dev(const void* state, int64_t joints, int64_t T, double* ou
  * "weight_bytes", "fft_loop" (hGRU contexts: 4 = the four-step FFT loop, 6 = the six-launch FFT
  * loop, 0 = a direct-convolution dtype, no FFT path); graph contexts also "graph_kernels" (kernel launches per forward),
  * "graph_streams" (streams the schedule uses), "graph_buffers" (activation buffers after concat placement), "graph_fused_pools" (2x2 max pools
- * computed inside their conv's kernel: MP_GRAPH_FUSE / MP_GRAPH_FUSE_POOL) -- as planned by the
- * last forward */
+ * computed inside their conv's kernel: MP_GRAPH_FUSE / MP_GRAPH_FUSE_POOL), "graph_fused_1x1" (1x1
+ * convs computed by a sibling's kernel) and "graph_path:<conv layer scope>" (the kernel the planned
+ * conv launches, an MP_PATH_* word, below) -- as planned by the last forward */
 int mp_info(mp_ctx* ctx, const char* key, int64_t* value);
+
+/* "graph_path:<scope>": which kernel family the planned conv of that scope launches, as decided by
+ * the dispatch itself (the launcher switches on the same value).  One word:
+ *   bits  0..7   family (MP_PATH_*)
+ *   bit   8      the conv's 2x2 max pool is fused into this kernel
+ *   bits 12..19  split-K count (1 = no split)
+ *   bits 20..23  halo family: pixel rows of waves, WR (MP_HALO_*)
+ *   bits 24..31  halo family: input channels per staged chunk, CH (16 or 32)
+ *   bits 32..35  halo family: filter size KS (3 or 5)
+ *   bits 36..39  pw / pwn: 32-channel input chunks, nch (1..6)
+ *   bits 40..43  pwn: 32-channel output blocks one block owns, nb (2..6); f32 / x3 im2col: NB (1, 2, 4)
+ * MP_PATH_SIBLING carries no other field: ask the sibling that leads the run for the kernel. */
+enum {
+  MP_PATH_F32_IM2COL = 1,      /* igemm_conv_kernel<NB>: exact fp32 (MP_DTYPE_F32, or K < 4)        */
+  MP_PATH_X3 = 2,              /* igemm_x3_kernel<NB>: f16-split im2col, Cout <= 64                 */
+  MP_PATH_X3W = 3,             /* igemm_x3w_kernel: wide im2col, Cout > 64                          */
+  MP_PATH_X3W_SPLITK = 4,      /* igemm_x3w_kernel over K slices + igemm_split_reduce_kernel        */
+  MP_PATH_PM = 5,              /* igemm_x3w_pm_kernel: position-major, padding taps skipped         */
+  MP_PATH_PM_SPLITK = 6,       /* igemm_x3w_pm_kernel over Cin ranges + igemm_pm_reduce_kernel      */
+  MP_PATH_HALO = 7,            /* igemm_x3h_kernel<KS, ., WR, CH>: halo tiles staged in LDS         */
+  MP_PATH_PW = 8,              /* igemm_x3pw_kernel<., nch>: 1x1, K <= 192                          */
+  MP_PATH_PWN = 9,             /* igemm_x3pwn_kernel<., nch, nb>: 1x1, one block per pixel tile     */
+  MP_PATH_CONV1_POOL_BN = 10,  /* 1 -> 64 channels 3x3 + relu + 2x2 max pool, dense output          */
+  MP_PATH_CONV1_POOL_ANY = 11, /* 1 -> C channels 3x3 + relu + 2x2 max pool into any output view    */
+  MP_PATH_SIBLING = 12         /* a 1x1 conv computed by a sibling's kernel (concatenated weights)  */
+};
+enum {
+  MP_HALO_TALL = 1,            /* Cout > 64 (default; MP_IGEMM_HALO_TALL=0 gives MP_HALO_WIDE)      */
+  MP_HALO_WIDE = 2,            /* Cout > 64 under MP_IGEMM_HALO_TALL=0 only                         */
+  MP_HALO_NARROW = 4,          /* Cout <= 64                                                        */
+  MP_HALO_NARROW1 = 8          /* Cout <= 32, no fused pool                                         */
+};
+#define MP_PATH_FAMILY(v) ((int)((v) & 0xff))
+#define MP_PATH_POOL(v) ((int)(((v) >> 8) & 1))
+#define MP_PATH_SPLITS(v) ((int)(((v) >> 12) & 0xff))
+#define MP_PATH_WR(v) ((int)(((v) >> 20) & 0xf))
+#define MP_PATH_CH(v) ((int)(((v) >> 24) & 0xff))
+#define MP_PATH_KS(v) ((int)(((v) >> 32) & 0xf))
+#define MP_PATH_NCH(v) ((int)(((v) >> 36) & 0xf))
+#define MP_PATH_NB(v) ((int)(((v) >> 40) & 0xf))
 
 /* per-kernel device timing with HIP events recorded on the launch stream around every launch of
  * kernel class `name` ("conv15_a", "conv15_b", "fc1", "backbone"); enable, run, then read the

@@ -165,6 +165,23 @@ def install(ctx: "_lib.Context", g: GraphRecorder, outputs: Sequence[Sym]) -> No
     del keep
 
 
+# MP_PATH_* / MP_HALO_* (include/monkeypose.h): the kernel family a planned conv launches
+PATH_FAMILIES = {1: "f32_im2col", 2: "x3", 3: "x3w", 4: "x3w_splitk", 5: "pm", 6: "pm_splitk", 7: "halo",
+                 8: "pw", 9: "pwn", 10: "conv1_pool_bn", 11: "conv1_pool_any", 12: "sibling"}
+HALO_LAYOUTS = {1: "tall", 2: "wide", 4: "narrow", 8: "narrow1"}
+
+
+def decode_path(v: int) -> dict:
+    """The fields of an ``mp_info(ctx, "graph_path:<scope>")`` word (MP_PATH_* macros)."""
+    return dict(family=PATH_FAMILIES[v & 0xff], pool=(v >> 8) & 1, splits=(v >> 12) & 0xff,
+                wr=(v >> 20) & 0xf, ch=(v >> 24) & 0xff, ks=(v >> 32) & 0xf, nch=(v >> 36) & 0xf,
+                nb=(v >> 40) & 0xf)
+
+
+def conv_path(ctx: "_lib.Context", scope: str) -> dict:
+    return decode_path(ctx.info("graph_path:" + scope))
+
+
 def layer_shapes(g: GraphRecorder) -> Dict[str, tuple]:
     """{layer scope: weight shape} for every conv (HWIO) and fc ([in, out]) of the graph."""
     d = {}

@@ -1409,10 +1409,18 @@ __global__ void pool2_kernel(const float* __restrict__ x, int ldx, int cix, int 
   out[pix * ldo + coff + c] = v;
 }
 
+IgemmPath igemm_conv_path(const IgemmArgs& a) {
+  const int N32 = (a.Cout + 31) / 32;
+  IgemmPath p;
+  p.family = MP_PATH_F32_IM2COL;
+  p.nb = N32 >= 4 ? 4 : (N32 >= 2 ? 2 : 1);
+  return p;
+}
+
 hipError_t launch_igemm_conv(const IgemmArgs& a, hipStream_t st) {
   const int M = a.N * a.Ho * a.Wo;
   const int N32 = (a.Cout + 31) / 32;
-  const int nb = N32 >= 4 ? 4 : (N32 >= 2 ? 2 : 1);
+  const int nb = igemm_conv_path(a).nb;
   dim3 grid((M + IG_BM - 1) / IG_BM, (N32 + nb - 1) / nb);
   if (nb == 4)
     hipLaunchKernelGGL(igemm_conv_kernel<4>, grid, dim3(256), 0, st, a);
@@ -1532,37 +1540,111 @@ bool igemm_can_pool(const IgemmArgs& a) {
   return pm_path(a) && a.part && igemm_pm_splits(a) > 1;   // the split-K reduce pools
 }
 
-hipError_t launch_igemm_x3(const IgemmArgs& a, const void* wpk, float unscale, hipStream_t st) {
-  if (a.K < 4) return hipErrorInvalidValue;   // the clamped vector load needs K >= 4
-  if (a.pool && !igemm_can_pool(a)) return hipErrorInvalidValue;
-  const int M = a.N * a.Ho * a.Wo;
+namespace {
+// the one place that chooses among the f16-split conv kernels; hg / lds are filled for the halo family
+IgemmPath x3_path(const IgemmArgs& a, HaloGeom& hg, size_t& lds) {
+  IgemmPath p;
+  p.pool = a.pool;
   const int N32 = (a.Cout + 31) / 32;
-  const int nb = N32 >= 4 ? 4 : (N32 >= 2 ? 2 : 1);
-  dim3 grid((M + IG_BM - 1) / IG_BM, (N32 + nb - 1) / nb);
-  const f16x8* w = static_cast<const f16x8*>(wpk);
-  const bool one = a.nprod == 1;   // MP_DTYPE_BF16: one f16 product per MAC
-  static const int xcd = env_flag("MP_IGEMM_XCD", 1);
   static const int pw = env_flag("MP_IGEMM_PW", 1);
   if (pw && a.KS == 1 && a.stride == 1 && a.Ho == a.H && a.Wo == a.W && a.pad_t == 0 && a.pad_l == 0 &&
       a.K == a.Cin && a.K <= 192 && a.Cin % 4 == 0 && a.cix % 4 == 0 && a.ldx % 4 == 0 && N32 <= 8 && !a.pool) {
-    const int nch = (a.K + 31) / 32;
-    const dim3 pgrid((M + IG_BM - 1) / IG_BM, (N32 + 3) / 4);   // 128-channel output tiles
-    IgemmArgs pa = a;
-    pa.xcd = xcd;
+    p.nch = std::min(6, (a.K + 31) / 32);
     // 2 .. 6 cout blocks: one block owns all of them (igemm_x3pwn_kernel).  MP_IGEMM_PWN for A/B:
     // 0 = the 2 x 2 wave grid everywhere; 1 = one block at 5 / 6 only (dense conv_6_1_1x1 0.630 ->
     // 0.420 ms); 2 = also 2 / 3, where the grid idles or clamps waves (conv_4_1_1x1 0.195 -> 0.176,
     // conv_3_1_1x1 0.127 -> 0.114, profiles/r3zp); 3 (default) = also 4 (conv_5_1_1x1 0.294 -> 0.254,
     // profiles/r3zw)
     static const int pwn = env_flag("MP_IGEMM_PWN", 3);
-    if ((pwn && (N32 == 5 || N32 == 6) && nch >= 4) || (pwn >= 2 && (N32 == 2 || N32 == 3)) ||
+    if ((pwn && (N32 == 5 || N32 == 6) && p.nch >= 4) || (pwn >= 2 && (N32 == 2 || N32 == 3)) ||
         (pwn == 3 && N32 == 4)) {
+      p.family = MP_PATH_PWN;
+      p.nb = N32;
+    } else {
+      p.family = MP_PATH_PW;
+    }
+    return p;
+  }
+  // halo tiles for Cout > 64, and (MP_IGEMM_HALO_NARROW, on by default) for Cout <= 64 with the
+  // four waves along the pixels (igemm_x3h_kernel<.., NARROW>): the im2col kernel gathers every
+  // input element KS^2 times
+  static const int narrow = env_flag("MP_IGEMM_HALO_NARROW", 1);
+  // (zero-padded Cin costs MFMAs: Cin = 12 padded to 32 was 2.7x and lost; the narrow halo path is
+  // taken where the padded channels are at most 4/3 of Cin -- 16-channel chunks make that 12 -> 16,
+  // 24 -> 32, 40 / 48 -> 48)
+  if ((wide_path(a) || (narrow && (a.Cin % 32 == 0 || 3 * (a.cinp ? a.cinp : a.Cin) <= 4 * a.Cin))) &&
+      halo_geom(a, hg, lds)) {
+    static const int tall = env_flag("MP_IGEMM_HALO_TALL", 1);
+    static const int narrow1 = env_flag("MP_IGEMM_HALO_NARROW1", 1);
+    p.family = MP_PATH_HALO;
+    p.ks = a.KS == 3 ? 3 : 5;
+    p.ch = 32;
+    if (narrow1 && N32 == 1 && !a.pool && halo_ch(a) == 16) {   // Cout <= 32 (NARROW1)
+      p.wr = MP_HALO_NARROW1;
+      p.ch = 16;
+    } else if (narrow1 && N32 == 1 && !a.pool) {
+      p.wr = MP_HALO_NARROW1;
+    } else if (N32 <= 2 && halo_ch(a) == 16) {   // Cout <= 64, 16-channel chunks
+      p.wr = MP_HALO_NARROW;
+      p.ch = 16;
+    } else if (N32 <= 2) {   // Cout <= 64
+      p.wr = MP_HALO_NARROW;
+    } else {
+      p.wr = tall ? MP_HALO_TALL : MP_HALO_WIDE;
+    }
+    return p;
+  }
+  if (wide_path(a)) {
+    const bool pm = pm_path(a);
+    const int S = pm && a.part ? igemm_pm_splits(a) : 1;
+    // split-K over K slices of the row-major wide kernel (igemm_x3w_splits)
+    const int S2 = !pm && a.part ? igemm_x3w_splits(a) : 1;
+    if (S > 1) {
+      p.family = MP_PATH_PM_SPLITK;
+      p.splits = S;
+    } else if (S2 > 1) {
+      p.family = MP_PATH_X3W_SPLITK;
+      p.splits = S2;
+    } else {
+      p.family = pm ? MP_PATH_PM : MP_PATH_X3W;
+    }
+    return p;
+  }
+  p.family = MP_PATH_X3;
+  p.nb = N32 >= 4 ? 4 : (N32 >= 2 ? 2 : 1);
+  return p;
+}
+}  // namespace
+
+IgemmPath igemm_x3_path(const IgemmArgs& a) {
+  HaloGeom hg;
+  size_t lds = 0;
+  return x3_path(a, hg, lds);
+}
+
+hipError_t launch_igemm_x3(const IgemmArgs& a, const void* wpk, float unscale, hipStream_t st) {
+  if (a.K < 4) return hipErrorInvalidValue;   // the clamped vector load needs K >= 4
+  if (a.pool && !igemm_can_pool(a)) return hipErrorInvalidValue;
+  const int M = a.N * a.Ho * a.Wo;
+  const int N32 = (a.Cout + 31) / 32;
+  const f16x8* w = static_cast<const f16x8*>(wpk);
+  const bool one = a.nprod == 1;   // MP_DTYPE_BF16: one f16 product per MAC
+  static const int xcd = env_flag("MP_IGEMM_XCD", 1);
+  HaloGeom hg;
+  size_t lds = 0;
+  const IgemmPath path = x3_path(a, hg, lds);
+  if (path.family == MP_PATH_PW || path.family == MP_PATH_PWN) {
+    const int nch = path.nch;
+    const dim3 pgrid((M + IG_BM - 1) / IG_BM, (N32 + 3) / 4);   // 128-channel output tiles
+    IgemmArgs pa = a;
+    pa.xcd = xcd;
+    if (path.family == MP_PATH_PWN) {
       const dim3 ngrid((M + IG_BM - 1) / IG_BM, 1);
 #define MP_PWX(NPV, NCHV, NBV) hipLaunchKernelGGL((igemm_x3pwn_kernel<NPV, NCHV, NBV>), ngrid, dim3(256), 0, st, pa, w, unscale)
 #define MP_PWXB(NCHV, NBV) \
   if (one) MP_PWX(1, NCHV, NBV); else MP_PWX(3, NCHV, NBV)
 #define MP_PWXN(NCHV)                  \
-  switch (N32) {                       \
+  switch (path.nb) {                   \
     case 2: MP_PWXB(NCHV, 2); break;   \
     case 3: MP_PWXB(NCHV, 3); break;   \
     case 4: MP_PWXB(NCHV, 4); break;   \
@@ -1598,17 +1680,7 @@ hipError_t launch_igemm_x3(const IgemmArgs& a, const void* wpk, float unscale, h
 #undef MP_PW
     return hipGetLastError();
   }
-  HaloGeom hg;
-  size_t lds = 0;
-  // halo tiles for Cout > 64, and (MP_IGEMM_HALO_NARROW, on by default) for Cout <= 64 with the
-  // four waves along the pixels (igemm_x3h_kernel<.., NARROW>): the im2col kernel gathers every
-  // input element KS^2 times
-  static const int narrow = env_flag("MP_IGEMM_HALO_NARROW", 1);
-  // (zero-padded Cin costs MFMAs: Cin = 12 padded to 32 was 2.7x and lost; the narrow halo path is
-  // taken where the padded channels are at most 4/3 of Cin -- 16-channel chunks make that 12 -> 16,
-  // 24 -> 32, 40 / 48 -> 48)
-  if ((wide_path(a) || (narrow && (a.Cin % 32 == 0 || 3 * (a.cinp ? a.cinp : a.Cin) <= 4 * a.Cin))) &&
-      halo_geom(a, hg, lds)) {
+  if (path.family == MP_PATH_HALO) {
     {
       static const bool attr = [] {
         for (const void* f : {reinterpret_cast<const void*>(igemm_x3h_kernel<3, 3, 2>),
@@ -1639,7 +1711,6 @@ hipError_t launch_igemm_x3(const IgemmArgs& a, const void* wpk, float unscale, h
         return true;
       }();
       (void)attr;
-      static const int tall = env_flag("MP_IGEMM_HALO_TALL", 1);
       const dim3 hgrid((M + IG_BM - 1) / IG_BM, N32 <= 2 ? 1 : (N32 + 3) / 4);
       IgemmArgs h = a;
       h.xcd = xcd;
@@ -1651,21 +1722,20 @@ hipError_t launch_igemm_x3(const IgemmArgs& a, const void* wpk, float unscale, h
 #define MP_HALO(KSV, NPV, WRV, CHV) \
   hipLaunchKernelGGL((igemm_x3h_kernel<KSV, NPV, WRV, CHV>), hgrid, dim3(256), lds, st, h, hg, w, unscale)
 #define MP_HALO_WRC(WRV, CHV)                    \
-  if (a.KS == 3 && one) MP_HALO(3, 1, WRV, CHV); \
-  else if (a.KS == 3) MP_HALO(3, 3, WRV, CHV);   \
+  if (path.ks == 3 && one) MP_HALO(3, 1, WRV, CHV); \
+  else if (path.ks == 3) MP_HALO(3, 3, WRV, CHV);   \
   else if (one) MP_HALO(5, 1, WRV, CHV);         \
   else MP_HALO(5, 3, WRV, CHV)
 #define MP_HALO_WR(WRV) MP_HALO_WRC(WRV, 32)
-      static const int narrow1 = env_flag("MP_IGEMM_HALO_NARROW1", 1);
-      if (narrow1 && N32 == 1 && !a.pool && halo_ch(a) == 16) {   // Cout <= 32 (NARROW1)
+      if (path.wr == MP_HALO_NARROW1 && path.ch == 16) {   // Cout <= 32 (NARROW1)
         MP_HALO_WRC(8, 16);
-      } else if (narrow1 && N32 == 1 && !a.pool) {
+      } else if (path.wr == MP_HALO_NARROW1) {
         MP_HALO_WR(8);
-      } else if (N32 <= 2 && halo_ch(a) == 16) {   // Cout <= 64, 16-channel chunks
+      } else if (path.wr == MP_HALO_NARROW && path.ch == 16) {   // Cout <= 64, 16-channel chunks
         MP_HALO_WRC(4, 16);
-      } else if (N32 <= 2) {   // Cout <= 64
+      } else if (path.wr == MP_HALO_NARROW) {   // Cout <= 64
         MP_HALO_WR(4);
-      } else if (tall) {
+      } else if (path.wr == MP_HALO_TALL) {
         MP_HALO_WR(1);
       } else {
         MP_HALO_WR(2);
@@ -1676,15 +1746,15 @@ hipError_t launch_igemm_x3(const IgemmArgs& a, const void* wpk, float unscale, h
       return hipGetLastError();
     }
   }
-  if (wide_path(a)) {
+  if (path.family != MP_PATH_X3) {   // the wide kernels (Cout > 64)
     IgemmArgs b = a;
     b.xcd = xcd;
-    b.pmajor = pm_path(a) ? 1 : 0;
-    const int S = b.pmajor && a.part ? igemm_pm_splits(a) : 1;
-    if (S > 1) {
+    b.pmajor = path.family == MP_PATH_PM || path.family == MP_PATH_PM_SPLITK;
+    if (path.family == MP_PATH_PM_SPLITK) {
       // split-K over input-channel ranges (z = range): raw partial sums to a.part, then a fixed-order
       // reduce with the epilogue -- 4x the blocks for the under-filled small-map convs (hier con_6:
       // 256 blocks of 128 x 128 on 256 CUs otherwise)
+      const int S = path.splits;
       const dim3 sgrid((M + IG_BM - 1) / IG_BM, (N32 + 3) / 4, S);
       if (one)
         hipLaunchKernelGGL(igemm_x3w_pm_kernel<1>, sgrid, dim3(256), 0, st, b, w, unscale);
@@ -1694,8 +1764,8 @@ hipError_t launch_igemm_x3(const IgemmArgs& a, const void* wpk, float unscale, h
       hipLaunchKernelGGL(igemm_pm_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, st, b, S, unscale);
       return hipGetLastError();
     }
-    const int S2 = !b.pmajor && a.part ? igemm_x3w_splits(a) : 1;
-    if (S2 > 1) {
+    if (path.family == MP_PATH_X3W_SPLITK) {
+      const int S2 = path.splits;
       const dim3 sgrid((M + IG_BM - 1) / IG_BM, (N32 + 3) / 4, S2);
       if (one)
         hipLaunchKernelGGL(igemm_x3w_kernel<1>, sgrid, dim3(256), 0, st, b, w, unscale);
@@ -1717,6 +1787,8 @@ hipError_t launch_igemm_x3(const IgemmArgs& a, const void* wpk, float unscale, h
       hipLaunchKernelGGL(igemm_x3w_kernel<3>, wgrid, dim3(256), 0, st, b, w, unscale);
     return hipGetLastError();
   }
+  const int nb = path.nb;
+  const dim3 grid((M + IG_BM - 1) / IG_BM, (N32 + nb - 1) / nb);
   if (nb == 4 && one)
     hipLaunchKernelGGL((igemm_x3_kernel<4, 1>), grid, dim3(256), 0, st, a, w, unscale);
   else if (nb == 4)

@@ -76,6 +76,7 @@ struct GraphState {
   // concatenated packings of fused 1x1 sibling convs, keyed by their names; kept across re-plans
   std::map<std::string, std::unique_ptr<mp_ctx::PackedLayer>> fused1x1;
   int n_fused_1x1 = 0;   // this plan's 1x1 convs computed by a sibling's kernel
+  std::vector<int> sib_lead;   // this plan: op -> the op whose kernel computes it (-1: its own)
   int64_t pn = 0, ph = 0, pw = 0;
   bool planned = false;
   std::vector<Tensor> t;
@@ -151,6 +152,11 @@ using G = GraphState;
 // for a conv whose only consumer is that pool (hier conv_1 -> pool_1): the pre-pool map is never
 // written (the hGRU backbone's conv_1 kernel, NHWC out, unit affine)
 constexpr int KIND_CONV1_POOL = 100;
+// its two forms: the hGRU backbone's conv_1 kernel for a dense 64-channel output (hier conv_1), else
+// the any-width form writing into the pool output's view (dense conv_0: 12 channels)
+int conv1_pool_family(const G::Kern& k) {
+  return k.pC == 64 && k.pldo == 64 && k.pcoff == 0 ? MP_PATH_CONV1_POOL_BN : MP_PATH_CONV1_POOL_ANY;
+}
 
 // 1x1 sibling fusion: the one packing of several 1x1 convs over the same input, output channels
 // concatenated in member order (weights [Cin][sum Cout], one power-of-two scale from their joint
@@ -287,7 +293,8 @@ void plan(mp_ctx* c, G& g, int64_t n, int64_t h, int64_t w) {
   // pointwise kernel takes it (Cin <= 192, Cout <= 256): the input is read once instead of once per
   // conv.  Their outputs become adjacent channel ranges of one buffer (placement constraints like a
   // concat's), so each consumer reads its slice in place.  MP_GRAPH_FUSE_1X1=0 keeps them apart.
-  std::vector<int> sib_lead(g.ops.size(), -1);        // op -> the op whose kernel computes it
+  g.sib_lead.assign(g.ops.size(), -1);
+  auto& sib_lead = g.sib_lead;                          // op -> the op whose kernel computes it
   std::vector<std::vector<int>> sib_mem(g.ops.size());  // lead -> members (lead first)
   g.n_fused_1x1 = 0;
   if (env_int("MP_GRAPH_FUSE_1X1", 1)) {
@@ -637,9 +644,7 @@ void launch_kern(mp_ctx* c, G& g, G::Kern& k, hipStream_t st) {
     case KIND_CONV1_POOL: {
       ProfScope ps(c, st, "graph_conv");
       ProfScope pl(c, st, g.ops[k.op].name.c_str());
-      // the hGRU backbone's conv_1 kernel for a dense 64-channel output (hier conv_1), else the
-      // any-width form writing into the pool output's view (dense conv_0: 12 channels)
-      if (k.pC == 64 && k.pldo == 64 && k.pcoff == 0)
+      if (conv1_pool_family(k) == MP_PATH_CONV1_POOL_BN)
         hip_check(launch_conv1_pool_bn(k.px, k.cw, k.cb, k.ones.f(), k.zeros.f(), k.pout, (int)g.pn, k.cH, k.cW, st,
                                        true),
                   g.ops[k.op].name.c_str());
@@ -776,6 +781,29 @@ bool graph_info(mp_ctx* c, const std::string& k, int64_t* v) {
     int64_t f = 0;
     for (const auto& kk : g.kerns) f += (kk->kind == MP_OP_CONV && kk->ia.pool) || kk->kind == KIND_CONV1_POOL;
     *v = f;
+  } else if (k.rfind("graph_path:", 0) == 0) {   // the kernel the planned conv launches (MP_PATH_*)
+    const std::string scope = strip_scope(k.c_str() + 11);
+    int oi = -1;
+    for (size_t i = 0; i < g.ops.size(); ++i)
+      if (g.ops[i].kind == MP_OP_CONV && g.ops[i].name == scope) oi = (int)i;
+    if (oi < 0) fail(MP_ERR_ARG, "graph_path: no conv layer named " + scope);
+    if (g.sib_lead[oi] >= 0 && g.sib_lead[oi] != oi) {
+      *v = MP_PATH_SIBLING;
+      return true;
+    }
+    for (const auto& kk : g.kerns) {
+      if (kk->op != oi) continue;
+      if (kk->kind == KIND_CONV1_POOL) {
+        IgemmPath p;
+        p.family = conv1_pool_family(*kk);
+        p.pool = 1;
+        *v = p.word();
+      } else {
+        *v = (kk->L->x3 ? igemm_x3_path(kk->ia) : igemm_conv_path(kk->ia)).word();
+      }
+      return true;
+    }
+    fail(MP_ERR_STATE, "graph_path: conv " + scope + " has no kernel in the plan");
   }
   else
     fail(MP_ERR_ARG, "unknown info key: " + k);

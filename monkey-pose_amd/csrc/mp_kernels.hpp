@@ -128,6 +128,21 @@ bool igemm_can_pool(const IgemmArgs& a);
 // of the layer alone (never of the batch), so every crop's sums group the same way at any batch
 int igemm_pm_splits(const IgemmArgs& a);
 size_t igemm_pm_part_floats(const IgemmArgs& a);
+// the kernel launch_igemm_x3 / launch_igemm_conv picks for these arguments (the launchers switch
+// on this value; mp_info "graph_path:<scope>" reports it)
+struct IgemmPath {
+  int family = 0;   // MP_PATH_* (include/monkeypose.h)
+  int pool = 0;     // the 2x2 max pool is fused
+  int splits = 1;   // split-K count
+  int wr = 0, ch = 0, ks = 0;   // halo: MP_HALO_* layout, channels per chunk, filter size
+  int nch = 0, nb = 0;          // pw / pwn: input chunks, output blocks; im2col: NB
+  int64_t word() const {
+    return (int64_t)family | (int64_t)(pool != 0) << 8 | (int64_t)splits << 12 | (int64_t)wr << 20 |
+           (int64_t)ch << 24 | (int64_t)ks << 32 | (int64_t)nch << 36 | (int64_t)nb << 40;
+  }
+};
+IgemmPath igemm_x3_path(const IgemmArgs& a);
+IgemmPath igemm_conv_path(const IgemmArgs& a);
 hipError_t launch_igemm_conv(const IgemmArgs& a, hipStream_t st);
 // f16x3 (fp32-accurate) variant; wpk packed by launch_pack_fc_x3 as a [K][Cout] matrix
 hipError_t launch_igemm_x3(const IgemmArgs& a, const void* wpk, float unscale, hipStream_t st);
