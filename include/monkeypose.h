@@ -189,6 +189,64 @@ int mp_hgru_circuit_fwd_ex(mp_ctx* ctx, const float* x, const float* o0, int64_t
 int mp_hgru_circuit_fwd_opts(mp_ctx* ctx, const float* x, const float* o0, int64_t n, int64_t h, int64_t w,
                              int64_t k, int timesteps, float* o_out, const mp_fwd_opts* opts, void* stream);
 
+/* ---- ContextualCircuit variants (the general loop) --------------------------------------------
+ * Every aux combination below runs through mp_hgru_circuit_fwd_var: per half-step the
+ * association-field conv writes a plain P map and one epilogue kernel applies the variant's rule
+ * (hgru_module.py:692-849).  The hgru_pose aux also runs here (for A/B against its fused loop).
+ * MP_DTYPE_F32, _F32_SPLIT and _F32_FFT; MP_DTYPE_BF16 with a variant is MP_ERR_UNSUPPORTED. */
+enum { MP_NL_TANH = 0, MP_NL_RELU = 1, MP_NL_SELU = 2, MP_NL_LEAKY_RELU = 3, MP_NL_HARD_TANH = 4 };
+enum { MP_INT_ALTERNATE = 0, MP_INT_MELY = 1, MP_INT_CONTROL = 2 };
+/* mp_circuit_variant.learned: the vectors that are weights ("contextual_circuit/<name>", [1,1,1,64]);
+ * one that is not learned is the constant 1 (prepare_tensors, 404-497) and is never asked of the
+ * caller.  kappa and omega are weights exactly when multiplicative_excitation is set. */
+enum { MP_CV_BETA = 1, MP_CV_NU = 2, MP_CV_ZETA = 4, MP_CV_GAMMA = 8, MP_CV_XI = 16, MP_CV_KAPPA = 32, MP_CV_OMEGA = 64 };
+/* struct_size = sizeof(mp_circuit_variant) as the caller was compiled (see mp_fwd_opts).  Zero-initialise. */
+typedef struct {
+  uint64_t struct_size;
+  int32_t gru_gates;                 /* 709-711 */
+  int32_t output_gru_gates;          /* 742-743 */
+  int32_t multiplicative_excitation; /* 784-793, 808-819 */
+  int32_t adaptation;                /* aux 'adapation': O' *= rho[t] (847-849); "contextual_circuit/rho"
+                                        is needed only then */
+  int32_t rectify;                   /* rectify_weights is False: P1 = min(P1, 0), P2 = max(P2, 0) */
+  int32_t recurrent_nl;              /* MP_NL_* */
+  int32_t integration;               /* MP_INT_* */
+  int32_t learned;                   /* MP_CV_* mask of the learned vectors */
+  int32_t lesion;                    /* MP_CV_BETA / _NU / _KAPPA / _OMEGA: the constant 0 (lesion_*) */
+  int32_t reserved;
+  /* MP_HIDDEN_RANDOM: O0 is the draw of seed rng_seed + rng_call, I0 that of rng_seed_i + rng_call
+   * (the reference draws the two states independently, 880-887) */
+  uint64_t rng_seed;
+  uint64_t rng_seed_i;
+  uint64_t rng_call;
+} mp_circuit_variant;
+
+/* fixes the variant an MP_MODEL_HGRU_CIRCUIT context will run; before mp_finalize_weights, which
+ * then asks only for the weights this variant reads and prepares the general loop's form of p_r
+ * (on MP_DTYPE_F32_FFT the six-launch spectral weights).  Such a context serves
+ * mp_hgru_circuit_fwd_var only; one without serves the fused entries only (MP_ERR_STATE otherwise). */
+int mp_circuit_set_variant(mp_ctx* ctx, const mp_circuit_variant* variant);
+
+/* ContextualCircuit(X, timesteps, ..., aux).build() for the context's variant.  x, o0, i0, o_out,
+ * i_out [n, h, w, 64] NHWC fp32; states_O / states_I [n, timesteps, h, w, 64] or NULL (every step's
+ * O_t after the rho gain / I_t).  hidden_init as in mp_fwd_opts, for both states (875-892): o0 and
+ * i0 are read with MP_HIDDEN_GIVEN only, and i0 only by a variant that reads the previous I
+ * (gru_gates unset with alternate / mely integration, or mely at all); i_out may be NULL.  variant:
+ * the flags the context was finalized with (MP_ERR_STATE if they differ) and this call's rng fields.
+ * Map sizes as for mp_hgru_circuit_fwd. */
+int mp_hgru_circuit_fwd_var(mp_ctx* ctx, const float* x, const float* o0, const float* i0, int64_t n, int64_t h,
+                            int64_t w, int64_t k, int timesteps, int hidden_init, const mp_circuit_variant* variant,
+                            float* o_out, float* i_out, float* states_O, float* states_I, void* stream);
+
+/* the variant's per-channel rule on host arrays (no GPU; the code the epilogue kernels compile):
+ * half 0: out = I' from P1, x, o, i (the previous I), gate = O . i_r + i_b
+ * half 1: out = O' from P2 (in p), i = I', o, gate = I' . o_r + o_b; x is not read
+ * p is the conv result before lateral_bias.  All arrays [npix][64]; consts [8][64] in the order
+ * lateral_bias, beta, nu, xi, gamma, kappa, omega, zeta, holding the values the variant resolves to. */
+int mp_circuit_var_rule_host(const mp_circuit_variant* variant, int half, int64_t npix, const float* p,
+                             const float* x, const float* o, const float* i, const float* gate,
+                             const float* consts, float rho, float* out);
+
 /* dense_model_struct.build(depth, output_shape) -> .output  (train_dense_networks.py:223-408):
  *   depth [n, h, w, 1] (h, w multiples of 32 in the reference's 128x128), out [n, output_shape] */
 int mp_dense_fwd(mp_ctx* ctx, const float* depth, int64_t n, int64_t h, int64_t w, float* out,

@@ -86,6 +86,14 @@ _SIGS = {
                                                 ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                 ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
                                                 ctypes.c_void_p, ctypes.c_void_p]),
+    "mp_circuit_set_variant": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "mp_hgru_circuit_fwd_var": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                               ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "mp_circuit_var_rule_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p]),
     "mp_dense_fwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                     ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     "mp_hier_fwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
@@ -152,6 +160,49 @@ def fwd_opts(hidden_init: int = 0, rng_seed: int = 0, rng_call: int = 0, states_
     o.states_O, o.states_I = _ptr(states_O), _ptr(states_I)
     o.taps = None if taps is None else ctypes.addressof(taps)
     return o
+
+
+MP_NL = {"tanh": 0, "relu": 1, "selu": 2, "leaky_relu": 3, "hard_tanh": 4}
+MP_INT = {"alternate": 0, "mely": 1, "control": 2}
+MP_CV = {"beta": 1, "nu": 2, "zeta": 4, "gamma": 8, "xi": 16, "kappa": 32, "omega": 64}
+# consts rows of mp_circuit_var_rule_host
+RULE_CONSTS = ("lateral_bias", "beta", "nu", "xi", "gamma", "kappa", "omega", "zeta")
+
+
+class CircuitVariant(ctypes.Structure):
+    """``mp_circuit_variant`` (include/monkeypose.h)."""
+    _fields_ = [("struct_size", ctypes.c_uint64)] + \
+               [(n, ctypes.c_int32) for n in ("gru_gates", "output_gru_gates", "multiplicative_excitation",
+                                              "adaptation", "rectify", "recurrent_nl", "integration", "learned",
+                                              "lesion", "reserved")] + \
+               [("rng_seed", ctypes.c_uint64), ("rng_seed_i", ctypes.c_uint64), ("rng_call", ctypes.c_uint64)]
+
+
+def circuit_variant(aux: dict, rng_seed: int = 0, rng_seed_i: int = 0, rng_call: int = 0) -> CircuitVariant:
+    """The variant of a ContextualCircuit aux dictionary (hgru_module.py:9-51 merged with the caller's)."""
+    v = CircuitVariant()
+    v.struct_size = ctypes.sizeof(CircuitVariant)
+    v.gru_gates = int(bool(aux['gru_gates']))
+    v.output_gru_gates = int(bool(aux['output_gru_gates']))
+    v.multiplicative_excitation = int(bool(aux['multiplicative_excitation']))
+    v.adaptation = int(bool(aux['adapation']))
+    v.rectify = int(aux['rectify_weights'] is False)
+    v.recurrent_nl = MP_NL[aux['recurrent_nl']]
+    v.integration = MP_INT[aux['integration_type']]
+    v.learned = sum(MP_CV[k] for k in ("beta", "nu", "zeta", "gamma", "xi") if aux[k])
+    v.lesion = sum(MP_CV[k] for k in ("beta", "nu", "kappa", "omega") if aux['lesion_' + k])
+    v.rng_seed, v.rng_seed_i, v.rng_call = int(rng_seed), int(rng_seed_i), int(rng_call)
+    return v
+
+
+def circuit_var_rule_host(variant: CircuitVariant, half: int, p, x, o, i, gate, consts, rho: float = 1.0):
+    """mp_circuit_var_rule_host on float32 numpy arrays [npix, 64] (consts [8, 64]); no GPU."""
+    arrs = [np.ascontiguousarray(a, np.float32) for a in (p, x, o, i, gate, consts)]
+    out = np.empty_like(arrs[0])
+    ptr = [a.ctypes.data_as(ctypes.c_void_p) for a in arrs]
+    check(load().mp_circuit_var_rule_host(ctypes.byref(variant), int(half), arrs[0].shape[0], *ptr,
+                                          ctypes.c_float(rho), out.ctypes.data_as(ctypes.c_void_p)))
+    return out
 
 
 class MonkeyPoseError(RuntimeError):
@@ -270,6 +321,16 @@ class Context:
         o = fwd_opts(hidden_init, rng_seed, rng_call, states_O, states_I)
         check(self.lib.mp_hgru_circuit_fwd_opts(self.h, _ptr(x), _ptr(o0), n, h, w, k, int(timesteps), _ptr(out),
                                                 ctypes.byref(o), ctypes.c_void_p(stream)))
+
+    def set_circuit_variant(self, variant: CircuitVariant) -> None:
+        check(self.lib.mp_circuit_set_variant(self.h, ctypes.byref(variant)))
+
+    def circuit_fwd_var(self, x, o0, i0, out, i_out, timesteps: int, stream: int, variant: CircuitVariant,
+                        hidden_init: int = 0, states_O=None, states_I=None) -> None:
+        n, h, w, k = x.shape
+        check(self.lib.mp_hgru_circuit_fwd_var(self.h, _ptr(x), _ptr(o0), _ptr(i0), n, h, w, k, int(timesteps),
+                                               int(hidden_init), ctypes.byref(variant), _ptr(out), _ptr(i_out),
+                                               _ptr(states_O), _ptr(states_I), ctypes.c_void_p(stream)))
 
     def dense_fwd(self, depth, out, stream: int) -> None:
         n, h, w, c = depth.shape

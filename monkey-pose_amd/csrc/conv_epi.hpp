@@ -57,6 +57,17 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, const f32x16& a
   if constexpr (EPI == EPI_BB) {
 #pragma unroll
     for (int n = 0; n < 2; ++n) bb_epilogue_n(p, acc[n], n, b, y, x, h);
+  } else if constexpr (EPI == EPI_PLAIN) {
+    // the conv result itself as a C8 map (the general circuit loop, k_circuit_var.hip)
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = acc[n][4 * g + j];
+        *reinterpret_cast<f32x4*>(p.dst + c8_index(b, 4 * n + g, y, x, 4 * h, H, W)) = o;
+      }
   } else if constexpr (EPI == EPI_HGRU_A) {
     // I = tanh(X - (beta*O + nu) * (P1 + lateral_bias))      hgru_module.py:657, 797-799
 #pragma unroll

@@ -350,6 +350,9 @@ hipError_t launch_conv64(int ks, int epi, ConvArgs a, int B, hipStream_t st) {
   MP_CASE(5, EPI_HGRU_B)
   MP_CASE(3, EPI_HGRU_A)
   MP_CASE(3, EPI_HGRU_B)
+  MP_CASE(15, EPI_PLAIN)
+  MP_CASE(5, EPI_PLAIN)
+  MP_CASE(3, EPI_PLAIN)
 #undef MP_CASE
   return hipErrorInvalidValue;
 }

@@ -323,6 +323,9 @@ hipError_t launch_conv64x3(int ks, int epi, ConvArgs a, const void* wpk, float u
   MP_CASE(3, EPI_HGRU_A)
   MP_CASE(3, EPI_HGRU_B)
   MP_CASE(3, EPI_BB)      // backbone conv_2 / conv_3 under MP_DTYPE_F32_SPLIT / _FFT
+  MP_CASE(15, EPI_PLAIN)
+  MP_CASE(5, EPI_PLAIN)
+  MP_CASE(3, EPI_PLAIN)
 #undef MP_CASE
   return hipErrorInvalidValue;
 }

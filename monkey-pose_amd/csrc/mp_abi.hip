@@ -88,7 +88,50 @@ void pack_x3(const RawWeight& w, DevBuf& out, int ks, float ascale, float* unsca
   hip_check(launch_pack_conv64x3(w.dev->f(), out.p, ks, wscale, nullptr), what);
 }
 
+// the vector table of a variant context (CV_VECS rows): a learned vector is the caller's weight, the
+// others the constants prepare_tensors gives them (hgru_module.py:404-497); rho only with adaptation
+void finalize_variant_vecs(mp_ctx* c) {
+  const mp_circuit_variant& m = c->var;
+  std::vector<float> v(CV_VECS * 64, 0.f);
+  auto put = [&](int row, const char* name, int bit, bool learned) {
+    float cst = 1.f;
+    if (m.lesion & bit) {
+      cst = 0.f;
+      learned = false;
+    }
+    if (learned) {
+      auto x = vec64(c, name);
+      std::copy(x.begin(), x.end(), v.begin() + row * 64);
+    } else {
+      std::fill(v.begin() + row * 64, v.begin() + (row + 1) * 64, cst);
+    }
+  };
+  put(V_LAT, "lateral_bias", 0, true);
+  put(V_IB, "i_b", 0, true);
+  put(V_OB, "o_b", 0, true);
+  put(V_BETA, "beta", MP_CV_BETA, (m.learned & MP_CV_BETA) != 0);
+  put(V_NU, "nu", MP_CV_NU, (m.learned & MP_CV_NU) != 0);
+  put(V_GAMMA, "gamma", 0, (m.learned & MP_CV_GAMMA) != 0);
+  put(V_KAPPA, "kappa", MP_CV_KAPPA, m.multiplicative_excitation != 0);
+  put(V_OMEGA, "omega", MP_CV_OMEGA, m.multiplicative_excitation != 0);
+  put(CV_ZETA, "zeta", 0, (m.learned & MP_CV_ZETA) != 0);
+  put(CV_XI, "xi", 0, (m.learned & MP_CV_XI) != 0);
+  std::fill(v.begin() + V_OUTS * 64, v.begin() + (V_OUTS + 1) * 64, 1.f);
+  upload(c->vecs, v);
+  c->rho.clear();
+  c->timesteps = 0;
+  if (m.adaptation) {
+    auto rt = c->raw.find("contextual_circuit/rho");
+    if (rt == c->raw.end() || rt->second.shape.size() != 1 || rt->second.shape[0] < 1)
+      fail(MP_ERR_WEIGHT, "contextual_circuit/rho must be set with shape [timesteps] (adaptation)");
+    c->rho = rt->second.host;
+    c->timesteps = (int)c->rho.size();
+  }
+}
+
 void finalize_circuit(mp_ctx* c, const std::vector<float>* outs, const std::vector<float>* outt) {
+  if (c->has_var && c->dtype == MP_DTYPE_BF16)
+    fail(MP_ERR_UNSUPPORTED, "circuit variants run MP_DTYPE_F32, _F32_SPLIT or _F32_FFT, not MP_DTYPE_BF16");
   auto it = c->raw.find("contextual_circuit/p_r");
   if (it == c->raw.end()) fail(MP_ERR_STATE, "weight not set: contextual_circuit/p_r");
   const auto& ps = it->second.shape;
@@ -103,7 +146,8 @@ void finalize_circuit(mp_ctx* c, const std::vector<float>* outs, const std::vect
   } else if (is_fft(c->dtype)) {
     const bool bf = c->dtype == MP_DTYPE_BF16;
     c->spec_g.alloc(fft_weight_bytes());
-    c->fft4 = fft4_enabled() && (c->dtype == MP_DTYPE_F32_FFT || (bf && fft_bf16_maps()));
+    // the general loop (has_var) runs launch_fft_fwd / _spec_gemm / _fft_inv: six-launch weights
+    c->fft4 = !c->has_var && fft4_enabled() && (c->dtype == MP_DTYPE_F32_FFT || (bf && fft_bf16_maps()));
     hip_check(build_spec_weights(it->second.dev->f(), c->ssf, c->spec_g.p, &c->p_unscale, bf, c->fft4), "p_r spectrum");
     c->or_x3.alloc(gate_x3_bytes());
     c->ir_x3.alloc(gate_x3_bytes());
@@ -120,6 +164,18 @@ void finalize_circuit(mp_ctx* c, const std::vector<float>* outs, const std::vect
             "pack i_r");
   hip_check(launch_pack_gate(c->need("contextual_circuit/o_r", {1, 1, 64, 64}).dev->f(), c->or_pk.v4(), nullptr),
             "pack o_r");
+  if (c->has_var) {
+    if (!is_fft(c->dtype)) {   // the epilogue kernels' f16x3 gates (the FFT branch above packed them)
+      c->or_x3.alloc(gate_x3_bytes());
+      c->ir_x3.alloc(gate_x3_bytes());
+      hip_check(pack_gate_x3(c->need("contextual_circuit/o_r", {1, 1, 64, 64}).dev->f(), c->or_x3.p, &c->or_us, false),
+                "pack o_r");
+      hip_check(pack_gate_x3(c->need("contextual_circuit/i_r", {1, 1, 64, 64}).dev->f(), c->ir_x3.p, &c->ir_us, false),
+                "pack i_r");
+    }
+    finalize_variant_vecs(c);
+    return;
+  }
   std::vector<float> v(V_COUNT * 64);
   const char* order[] = {"lateral_bias", "beta", "nu", "gamma", "kappa", "omega", "i_b", "o_b"};
   for (int k = 0; k < 8; ++k) {
@@ -660,6 +716,102 @@ const float* hidden_state(mp_ctx* c, int hidden_init, const float* o0, const flo
   return nullptr;
 }
 
+// ---- the general ContextualCircuit loop (every variant outside the fused pose configuration) ----
+// per half-step: conv -> plain P map -> epilogue kernel (k_circuit_var.hip).  X, O, I and the conv
+// inputs Og (gru_gates: O g1) and bufA (output_gru_gates: I' g2) are C8 maps; P (specP) is C8 from
+// the direct convs and launch_fft_inv's layout on the FFT path.  One stream, no batch slices.
+
+// mp_circuit_variant as the caller compiled it (see read_opts)
+mp_circuit_variant read_variant(const mp_circuit_variant* v) {
+  if (!v) fail(MP_ERR_ARG, "variant is NULL");
+  if (v->struct_size < offsetof(mp_circuit_variant, reserved))
+    fail(MP_ERR_ARG, "mp_circuit_variant.struct_size is smaller than its first layout");
+  mp_circuit_variant m{};
+  std::memcpy(&m, v, std::min<size_t>((size_t)v->struct_size, sizeof(m)));
+  if (m.recurrent_nl < 0 || m.recurrent_nl >= mpcv::NL_COUNT) fail(MP_ERR_ARG, "recurrent_nl must be an MP_NL_* value");
+  if (m.integration < 0 || m.integration >= mpcv::INT_COUNT) fail(MP_ERR_ARG, "integration must be an MP_INT_* value");
+  return m;
+}
+
+mpcv::CircuitVariant pod_variant(const mp_circuit_variant& m) {
+  return mpcv::make_variant(m.gru_gates != 0, m.output_gru_gates != 0, m.rectify != 0,
+                            m.multiplicative_excitation != 0, m.adaptation != 0, m.recurrent_nl, m.integration);
+}
+
+bool same_flags(const mp_circuit_variant& a, const mp_circuit_variant& b) {
+  return a.gru_gates == b.gru_gates && a.output_gru_gates == b.output_gru_gates &&
+         a.multiplicative_excitation == b.multiplicative_excitation && a.adaptation == b.adaptation &&
+         a.rectify == b.rectify && a.recurrent_nl == b.recurrent_nl && a.integration == b.integration &&
+         a.learned == b.learned && a.lesion == b.lesion;
+}
+
+// P = p_r * src (no bias, no epilogue) in the context's precision
+void plain_conv(mp_ctx* c, const float* src, int n, int H, int W, hipStream_t st) {
+  ProfScope ps(c, st, "var_conv");
+  if (is_fft(c->dtype)) {
+    hip_check(launch_fft_fwd(src, c->specS.p, n, H, W, st, false), "fft_fwd");
+    hip_check(launch_spec_gemm(c->specS.p, c->spec_g.p, c->specY.p, n, c->p_unscale, st, false), "spec_gemm");
+    hip_check(launch_fft_inv(c->specY.p, c->specP.f(), n, H, W, st, false), "fft_inv");
+    return;
+  }
+  ConvArgs a{};
+  a.H = H;
+  a.W = W;
+  a.src = src;
+  a.wpk = c->p_pk.v4();
+  a.dst = c->specP.f();
+  eCRF_conv(c, EPI_PLAIN, a, n, st);
+}
+
+void var_circuit(mp_ctx* c, int n, int H, int W, int T, const float* o0_nhwc, const float* i0_nhwc, float* o_out,
+                 float* i_out, const StateOut* so, hipStream_t st) {
+  const mpcv::CircuitVariant v = c->cv;
+  const size_t bytes = c->X.bytes;
+  if (!is_fft(c->dtype)) c->specP.alloc(bytes);
+  c->Og.alloc(bytes);
+  if (v.out_gates) c->bufA.alloc(bytes);
+  if (v.gru_gates)   // O0 -> O, and the first A_in = O0 * sigmoid(O0 . i_r + i_b)   (696-711)
+    hip_check(launch_gate_init(o0_nhwc, c->O.f(), c->Og.f(), c->ir_pk.v4(), c->vecs.f(), n, H, W, st), "gate_init");
+  else
+    hip_check(launch_nhwc_to_c8(o0_nhwc, c->O.f(), n, H, W, st), "O0");
+  if (mpcv::reads_prev_i(v)) hip_check(launch_nhwc_to_c8(i0_nhwc, c->I.f(), n, H, W, st), "I0");
+  CvArgs a{};
+  a.v = v;
+  a.P = c->specP.f();
+  a.X = c->X.f();
+  a.O = c->O.f();
+  a.I = c->I.f();
+  a.Bin = v.out_gates ? c->bufA.f() : nullptr;
+  a.Ain = c->Og.f();
+  a.vecs = c->vecs.f();
+  a.gpk_ir = c->ir_pk.v4();
+  a.gpk_or = c->or_pk.v4();
+  a.ir_x3 = c->ir_x3.p;
+  a.or_x3 = c->or_x3.p;
+  a.ir_us = c->ir_us;
+  a.or_us = c->or_us;
+  a.H = H;
+  a.W = W;
+  a.p_fft = is_fft(c->dtype) ? 1 : 0;
+  for (int t = 0; t < T; ++t) {
+    plain_conv(c, v.gru_gates ? c->Og.f() : c->O.f(), n, H, W, st);
+    {
+      ProfScope ps(c, st, "var_in");
+      a.out = nullptr;
+      hip_check(launch_circuit_in(a, n, st), "circuit input half");
+    }
+    plain_conv(c, v.out_gates ? c->bufA.f() : c->I.f(), n, H, W, st);
+    {
+      ProfScope ps(c, st, "var_out");
+      a.rho = v.adapt ? c->rho[t] : 1.f;
+      a.out = t == T - 1 ? o_out : nullptr;
+      hip_check(launch_circuit_out(a, n, st), "circuit output half");
+    }
+    store_step(so, c->O.f(), c->I.f(), 0, n, H, W, t, false, st);
+  }
+  if (i_out) hip_check(launch_c8_to_nhwc(c->I.f(), i_out, n, H, W, st), "final I");
+}
+
 }  // namespace
 
 // ================================================ C ABI ============================================
@@ -1096,6 +1248,8 @@ int mp_hgru_circuit_fwd_opts(mp_ctx* ctx, const float* x, const float* o0, int64
     if (!ctx || !x || !o_out || (!o0 && hidden_init == MP_HIDDEN_GIVEN))
       fail(MP_ERR_ARG, "mp_hgru_circuit_fwd: null pointer");
     if (!ctx->finalized) fail(MP_ERR_STATE, "weights not finalized");
+    if (ctx->has_var)
+      fail(MP_ERR_STATE, "context finalized for a circuit variant: use mp_hgru_circuit_fwd_var");
     if (k != 64) fail(MP_ERR_SHAPE, "channel count k must be 64");
     if (n <= 0 || h <= 0 || w <= 0) fail(MP_ERR_SHAPE, "empty input");
     check_map(ctx, h, w, "x");
@@ -1115,6 +1269,89 @@ int mp_hgru_circuit_fwd_opts(mp_ctx* ctx, const float* x, const float* o0, int64
     so.I = states_I;
     so.T = timesteps;
     run_circuit(ctx, n, (int)h, (int)w, timesteps, h0, o_out, (states_O || states_I) ? &so : nullptr, st);
+  });
+}
+
+int mp_circuit_set_variant(mp_ctx* ctx, const mp_circuit_variant* variant) {
+  return guard([&] {
+    if (!ctx) fail(MP_ERR_ARG, "ctx is NULL");
+    if (ctx->model != MP_MODEL_HGRU_CIRCUIT)
+      fail(MP_ERR_STATE, "circuit variants run on an MP_MODEL_HGRU_CIRCUIT context");
+    ctx->var = read_variant(variant);
+    ctx->cv = pod_variant(ctx->var);
+    ctx->has_var = true;
+    ctx->finalized = false;
+    ctx->cap_batch = 0;   // the general loop's workspace differs from the fused loops': size it again
+    ctx->cap_hw = 0;
+  });
+}
+
+int mp_hgru_circuit_fwd_var(mp_ctx* ctx, const float* x, const float* o0, const float* i0, int64_t n, int64_t h,
+                            int64_t w, int64_t k, int timesteps, int hidden_init, const mp_circuit_variant* variant,
+                            float* o_out, float* i_out, float* states_O, float* states_I, void* stream) {
+  return guard([&] {
+    if (!ctx || !x || !o_out) fail(MP_ERR_ARG, "mp_hgru_circuit_fwd_var: null pointer");
+    if (!ctx->finalized) fail(MP_ERR_STATE, "weights not finalized");
+    if (!ctx->has_var) fail(MP_ERR_STATE, "context has no circuit variant: mp_circuit_set_variant before finalizing");
+    const mp_circuit_variant m = read_variant(variant);
+    if (!same_flags(m, ctx->var)) fail(MP_ERR_STATE, "variant differs from the one the context was finalized with");
+    const bool live_i = mpcv::reads_prev_i(ctx->cv);
+    if (hidden_init == MP_HIDDEN_GIVEN && (!o0 || (live_i && !i0)))
+      fail(MP_ERR_ARG, "o0 / i0 is NULL (hidden_init = MP_HIDDEN_GIVEN)");
+    if (k != 64) fail(MP_ERR_SHAPE, "channel count k must be 64");
+    if (n <= 0 || h <= 0 || w <= 0 || n * h * w > (int64_t)1 << 24) fail(MP_ERR_SHAPE, "empty or oversized input");
+    check_map(ctx, h, w, "x");
+    if (timesteps < 1 || (ctx->cv.adapt && timesteps > (int)ctx->rho.size()))
+      fail(MP_ERR_ARG, "timesteps must be at least 1 and, with adaptation, at most len(rho)");
+    hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    ensure_ws(ctx, n, h, w);
+    hip_check(launch_nhwc_to_c8(x, ctx->X.f(), (int)n, (int)h, (int)w, st), "nhwc_to_c8");
+    const float* h0 = hidden_state(ctx, hidden_init, o0, x, n, (int)h, (int)w, st, m.rng_seed + m.rng_call);
+    const float* hi = nullptr;
+    if (live_i) {   // the initial I, made like O0 (hgru_module.py:875-892)
+      const size_t bytes = (size_t)n * h * w * 64 * sizeof(float);
+      switch (hidden_init) {
+        case MP_HIDDEN_GIVEN: hi = i0; break;
+        case MP_HIDDEN_IDENTITY: hi = x; break;
+        case MP_HIDDEN_ZEROS:
+          ctx->i0.alloc(bytes);
+          hip_check(hipMemsetAsync(ctx->i0.p, 0, bytes, st), "hidden_init zeros (I)");
+          hi = ctx->i0.f();
+          break;
+        default:   // MP_HIDDEN_RANDOM (hidden_state checked the value): a second, independent draw
+          ctx->i0.alloc(bytes);
+          hip_check(launch_hidden_uniform(ctx->i0.f(), n * h * w * 64, m.rng_seed_i + m.rng_call,
+                                          std::sqrt(6.0 / (2 * 64)), st),
+                    "hidden_init random (I)");
+          hi = ctx->i0.f();
+      }
+    }
+    StateOut so;
+    so.O = states_O;
+    so.I = states_I;
+    so.T = timesteps;
+    var_circuit(ctx, (int)n, (int)h, (int)w, timesteps, h0, hi, o_out, i_out, (states_O || states_I) ? &so : nullptr,
+                st);
+  });
+}
+
+int mp_circuit_var_rule_host(const mp_circuit_variant* variant, int half, int64_t npix, const float* p,
+                             const float* x, const float* o, const float* i, const float* gate,
+                             const float* consts, float rho, float* out) {
+  return guard([&] {
+    const mp_circuit_variant m = read_variant(variant);
+    if (half < 0 || half > 1 || npix < 0 || !p || !o || !i || !gate || !consts || !out || (half == 0 && !x))
+      fail(MP_ERR_ARG, "mp_circuit_var_rule_host: bad argument");
+    const mpcv::CircuitVariant v = pod_variant(m);
+    for (int64_t e = 0; e < npix * 64; ++e) {
+      const int c = (int)(e % 64);
+      auto k = [&](int row) { return consts[row * 64 + c]; };
+      if (half == 0)
+        out[e] = mpcv::rule_in_any(v, p[e], x[e], o[e], i[e], gate[e], mpcv::InConst{k(0), k(1), k(2), k(3)});
+      else
+        out[e] = mpcv::rule_out_any(v, p[e], i[e], o[e], gate[e], rho, mpcv::OutConst{k(0), k(4), k(5), k(6), k(7)});
+    }
   });
 }
 

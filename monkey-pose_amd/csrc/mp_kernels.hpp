@@ -1,12 +1,14 @@
 // Launcher declarations shared by the kernel translation units and the C-ABI layer.
 #pragma once
 #include "mp_common.hpp"
+#include "circuit_var.hpp"
 #include "../../include/monkeypose.h"
 
 namespace mp {
 
 constexpr int TH = 16, TW = 32;   // conv64 output tile (pixels) per 256-thread block
-enum Epi { EPI_BB = 0, EPI_HGRU_A = 1, EPI_HGRU_B = 2 };
+// EPI_PLAIN: acc * scale stored as a C8 map (the general circuit loop's P, k_circuit_var.hip)
+enum Epi { EPI_BB = 0, EPI_HGRU_A = 1, EPI_HGRU_B = 2, EPI_PLAIN = 3 };
 
 struct ConvArgs {
   const float* src;       // conv input, C8
@@ -97,6 +99,31 @@ hipError_t launch_col_gemm(void* Z, const void* Gc, int B, float unscale, hipStr
                            int ntot = 1 << 30);
 hipError_t launch_row(int mode, void* Z, const ConvArgs& a, const void* or_x3, float or_us, const void* ir_x3,
                       float ir_us, const float* O0, int B, hipStream_t st, bool bf = false, int ntot = 1 << 30);
+// k_circuit_var.hip: the epilogue kernels of the general ContextualCircuit loop.  The variant's
+// vector table is the fused loop's (VecId) with zeta and xi appended
+constexpr int CV_ZETA = V_COUNT, CV_XI = V_COUNT + 1, CV_VECS = V_COUNT + 2;
+struct CvArgs {
+  mpcv::CircuitVariant v;
+  const float* P;        // the conv result before lateral_bias: C8, or (p_fft) launch_fft_inv's layout
+  const float* X;        // in: the drive (C8)
+  float* O;              // in: O (C8, read);  out: O, updated in place to O'
+  float* I;              // in: the previous I, updated in place to I';  out: I' (C8, read)
+  float* Bin;            // in, output_gru_gates: I' * g2 (C8), the next conv's input
+  float* Ain;            // out, gru_gates, not the last step: O' * g1 (C8), the next conv's input
+  float* out;            // out, the last step: O_T NHWC fp32 (null on the other steps)
+  const float* vecs;     // [CV_VECS][64]
+  const f32x4* gpk_ir;   // i_r / o_r packed by launch_pack_gate
+  const f32x4* gpk_or;
+  const void* ir_x3;     // i_r / o_r packed by pack_gate_x3 (the bounded nonlinearities' gates)
+  const void* or_x3;
+  float ir_us, or_us;
+  float rho;             // out: rho[t] (read with adapt)
+  int H, W;
+  int p_fft;
+  bool integration_ok() const { return v.nl < mpcv::NL_COUNT && v.integration < mpcv::INT_COUNT; }
+};
+hipError_t launch_circuit_in(const CvArgs& a, int B, hipStream_t st);
+hipError_t launch_circuit_out(const CvArgs& a, int B, hipStream_t st);
 // k_igemm.hip (dense / hierarchical regressors)
 struct IgemmArgs {
   const float* x;      // input view: pixel (n,y,x) channel ci at x[((n*H+y)*W+x)*ldx + cix + ci]

@@ -83,6 +83,8 @@ inline bool known_name_hgru(int model, const std::string& n) {
                                   "omega", "rho", "lateral_bias"};
   for (auto c : circuit)
     if (n == std::string("contextual_circuit/") + c) return true;
+  // learned only by variants of the standalone circuit (mp_circuit_set_variant)
+  if (model == MP_MODEL_HGRU_CIRCUIT && (n == "contextual_circuit/zeta" || n == "contextual_circuit/xi")) return true;
   if (model == MP_MODEL_HGRU_CIRCUIT) return false;
   for (const char* l : {"conv_1", "conv_2", "conv_3"})
     if (n == std::string(l) + "/" + l + "_filters" || n == std::string(l) + "/" + l + "_biases") return true;
@@ -129,6 +131,11 @@ struct mp_ctx {
   bool fft4 = false;        // the fp32 FFT path runs k_fft4.hip's four-step loop (class-major spec_g)
   DevBuf or_x3, ir_x3;      // MP_DTYPE_F32_FFT: o_r / i_r packed for the f16x3 gate GEMMs
   float or_us = 1.f, ir_us = 1.f;
+  // a circuit context finalized for the general loop (mp_circuit_set_variant): vecs then holds
+  // CV_VECS rows (the variant's constants filled in) and spec_g the six-launch spectral weights
+  bool has_var = false;
+  mp_circuit_variant var{};
+  mpcv::CircuitVariant cv{};
   DevBuf fc1_pk, fc1_b, bn4_s, bn4_t, fco_pk, fco_b;
   float fc1_unscale = 1.f;   // fc_1 packed f16x3 (dtype F32_SPLIT / F32_FFT): 1 / weight scale
 
@@ -137,6 +144,7 @@ struct mp_ctx {
   int64_t cap_hw = 0;
   DevBuf bufA, bufB, X, O, I, Og, fcin, part, part2, h1;   // part2: fc_out's partials (per-slice heads)
   DevBuf h0;                // hidden_init zeros / identity: the NHWC initial state (allocated on use)
+  DevBuf i0;                // general loop, MP_HIDDEN_RANDOM: the NHWC draw of the initial I
   DevBuf specS, specY, specP;   // MP_DTYPE_F32_FFT: input / output spectra, spatial conv result
 
   // ---- dense / hierarchical regressors (mp_regressors.hip) ----

@@ -204,6 +204,11 @@ class model:
         return self.forward(depth, h2_init, keep_intermediates, store_states)
 
     def _hidden_init(self) -> str:
+        from .hgru_module import is_pose_aux, merged_aux
+        if not is_pose_aux(merged_aux(self.aux)):
+            raise NotImplementedError("hgru_pose.model runs its own aux only (hgru_pose.py:20-39): BN_3 and fc_1's "
+                                      "input planes are fused into the hGRU loop's last kernel; other variants run "
+                                      "through hgru_module.ContextualCircuit")
         hi = self.aux.get('hidden_init', 'random')
         if hi not in _lib.MP_HIDDEN:
             raise NotImplementedError(f"aux hidden_init={hi!r}: the reference raises (hgru_module.py:891-892)")

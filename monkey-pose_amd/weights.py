@@ -109,17 +109,25 @@ def _fc(scope: str, nin: int, nout: int) -> List[Var]:
 
 
 def hgru_circuit_vars(k: int = 64, ssf: int = 15, gate_filter: int = 1, timesteps: int = 8,
-                      scope: str = "cnn/contextual_circuit") -> List[Var]:
-    """``prepare_tensors`` with the hgru_pose aux (``hgru_pose.py:20-39``): association field,
-    gru gates, gamma, multiplicative excitation, adaptation (rho); xi/zeta constant 1."""
+                      scope: str = "cnn/contextual_circuit", *, beta: bool = True, nu: bool = True,
+                      zeta: bool = False, gamma: bool = True, xi: bool = False, kappa: bool = True,
+                      omega: bool = True, rho: bool = True) -> List[Var]:
+    """``prepare_tensors`` (``hgru_module.py:298-503``) in creation order.  The keyword flags say
+    which of the optional variables the aux creates (a vector that is not created is a constant,
+    404-497; rho exists only with adaptation); the defaults are the hgru_pose aux
+    (``hgru_pose.py:20-39``): association field, gru gates, gamma, multiplicative excitation,
+    adaptation (rho); xi/zeta constant 1."""
     v = [Var(f"{scope}/p_r", (ssf, ssf, k, k), "glorot"),                    # 298-310
          Var(f"{scope}/i_r", (gate_filter, gate_filter, k, k), "glorot"),    # 322-332
          Var(f"{scope}/i_b", (1, 1, 1, k), "chronos"),                       # 344-357
          Var(f"{scope}/o_r", (gate_filter, gate_filter, k, k), "glorot"),    # 360-370
          Var(f"{scope}/o_b", (1, 1, 1, k), "neg_chronos")]                   # 382-396
-    for nm in ("beta", "nu", "gamma", "kappa", "omega"):                    # 405-486
-        v.append(Var(f"{scope}/{nm}", (1, 1, 1, k), "glorot"))
-    v.append(Var(f"{scope}/rho", (timesteps,), "ones"))                      # 490-493
+    made = dict(beta=beta, nu=nu, zeta=zeta, gamma=gamma, xi=xi, kappa=kappa, omega=omega)
+    for nm in ("beta", "nu", "zeta", "gamma", "xi", "kappa", "omega"):      # 405-486
+        if made[nm]:
+            v.append(Var(f"{scope}/{nm}", (1, 1, 1, k), "glorot"))
+    if rho:
+        v.append(Var(f"{scope}/rho", (timesteps,), "ones"))                  # 490-493
     v.append(Var(f"{scope}/lateral_bias", (1, 1, 1, k), "glorot"))           # 498-503
     return v
 

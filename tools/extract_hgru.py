@@ -364,7 +364,19 @@ class Interp:
                 out.append(self.expr(e.elt, g, inner))
             return out
         if isinstance(e, ast.Lambda):
-            raise NotImplementedError("lambda")
+            # positional parameters only (hard_tanh, hgru_module.py:141)
+            a = e.args
+            if a.vararg or a.kwarg or a.kwonlyargs or a.defaults:
+                raise NotImplementedError("lambda with defaults / varargs")
+            names = [x.arg for x in a.args]
+
+            def fn(*args):
+                if len(args) != len(names):
+                    raise TypeError("lambda: wrong number of arguments")
+                inner = dict(env)
+                inner.update(zip(names, args))
+                return self.expr(e.body, g, inner)
+            return fn
         raise NotImplementedError(ast.dump(e))
 
 
@@ -497,9 +509,17 @@ def make_tf(interp: Interp):
         shape = tuple(x.shape[p] for p in perm)
         return S.mk("transpose", [x, tuple(perm)], shape)
 
+    # selu / leaky_relu have no node of their own in tests/symbolic.py: opaque named nodes (the
+    # variant oracle, tests/hgru_variants_ref.py, builds the same ones), alpha = TF's default 0.2
+    def selu(x, name=None):
+        return S.mk("selu", [x], x.shape)
+
+    def leaky_relu(x, alpha=0.2, name=None):
+        return S.mk("leaky_relu", [x, float(alpha)], x.shape)
+
     nn = types.SimpleNamespace(
         conv2d=conv2d, bias_add=lambda x, b: S.add(x, b), relu=S.relu, tanh=S.tanh, sigmoid=S.sigmoid,
-        max_pool=max_pool, dropout=None, atrous_conv2d=None)
+        max_pool=max_pool, dropout=None, atrous_conv2d=None, selu=selu, leaky_relu=leaky_relu)
     tf = types.SimpleNamespace(
         nn=nn, layers=types.SimpleNamespace(batch_normalization=batch_normalization),
         float32="float32", constant=constant, get_variable=get_variable, variable_scope=VarScope,
@@ -550,7 +570,10 @@ def _patch_shapes(g):
     S.Sym.get_shape = lambda self: _sym_shape(self)
 
     def set_shape(self, shape):
-        if [int(x) for x in shape] != list(self.shape):
+        # a node's recorded shape is that of its first longest operand (symbolic._bshape), which for
+        # a sum led by a [1, 1, 1, k] vector is the vector's: size-1 axes stand for broadcast ones
+        want = [int(x) for x in shape]
+        if len(want) != len(self.shape) or any(a != b and a != 1 for a, b in zip(self.shape, want)):
             raise ValueError(f"set_shape {shape} on {self.shape}")
     S.Sym.set_shape = set_shape
 
@@ -577,11 +600,14 @@ def pose_aux():
     return dict(model().get("aux", None))
 
 
-def circuit(n, h, w, ssf, timesteps, hidden_init="random", store_states=False):
+def circuit(n, h, w, ssf, timesteps, hidden_init="random", store_states=False, aux_overrides=None,
+            pose_aux=True):
     """ContextualCircuit(X, timesteps, SRF=1, SSN=15, SSF=ssf, aux=hgru_pose aux + overrides).build()
-    with X an input named 'X'; returns (interp, O, weights-dict)"""
+    with X an input named 'X'; returns (interp, O, weights-dict).  ``pose_aux=False`` starts from
+    the module's own defaults (no aux but the overrides) instead of the hgru_pose aux."""
     interp, cc, model = load()
-    aux = dict(model().get("aux", interp))
+    aux = dict(model().get("aux", interp)) if pose_aux else {}
+    aux.update(aux_overrides or {})
     aux["hidden_init"] = hidden_init
     aux["store_states"] = store_states
     X = S.inp("X", (n, h, w, 64))

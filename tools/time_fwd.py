@@ -9,7 +9,9 @@ import time
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# AB_ROOT: time another checkout's package and library (a built copy of the parent commit) with this
+# script, so that tools/ab_time.sh interleaves two trees like two settings
+ROOT = os.environ.get("AB_ROOT") or os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 mp = importlib.import_module("monkey-pose_amd")
 W = mp.weights
@@ -41,6 +43,6 @@ for _ in range(a.reps):
     torch.cuda.synchronize()
     ts.append((time.perf_counter() - t0) / a.steps * 1e3)
 ts.sort()
-env = {k: v for k, v in os.environ.items() if k.startswith("MP_")}
+env = {k: v for k, v in os.environ.items() if k.startswith("MP_") or k == "AB_ROOT"}
 print(json.dumps({"env": env, "dtype": a.dtype, "batch": B, "ms_median": round(ts[len(ts) // 2], 4),
                   "ms_min": round(ts[0], 4), "ms_all": [round(t, 4) for t in ts]}), flush=True)
