@@ -69,7 +69,7 @@ enum { MP_MEM_HOST = 0, MP_MEM_DEVICE = 1 };
  *                       for maps up to 64x64): fp32 72-point FFTs + a per-frequency complex
  *                       channel GEMM in the f16x3 split (three v_mfma_f32_32x32x16_f16 per complex
  *                       MAC term, fp32 accumulation); ~50x fewer FLOPs than direct at 15x15 taps,
- *                       error ~1e-6 of max|output|.  Needs map height <= 64, width 32 or 64.
+ *                       error ~1e-6 of max|output|.  Needs map height in [1, 64], width 32 or 64.
  *   MP_DTYPE_BF16       the FFT path with bf16 spectra (input and output), bf16 spectral weights and
  *                       bf16 1x1 gate weights: one v_mfma_f32_32x32x16_bf16 product per MAC, fp32
  *                       accumulation, fp32 FFTs and elementwise math; the hGRU maps O / I / Og / P2
@@ -173,7 +173,13 @@ int mp_hgru_pose_fwd_taps(mp_ctx* ctx, const float* depth, int64_t n, int64_t h,
                           const float* o0, float* out, const mp_pose_taps* taps, void* stream);
 
 /* ContextualCircuit(X, timesteps, ...).build() -> O  (hgru_module.py:872-959), hgru_pose aux:
- *   x, o0, o_out  [n, h, w, k] NHWC; k must be 64, h % 16 == 0, w % 32 == 0;
+ *   x, o0, o_out  [n, h, w, k] NHWC; k must be 64;
+ *   map size, by the dtype the context was finalized with (MP_ERR_SHAPE otherwise, before any launch):
+ *     MP_DTYPE_F32_FFT, MP_DTYPE_BF16   any h in [1, 64] (rows past h are zero padding of the 72-point
+ *                                       transforms), w == 32 or w == 64
+ *     MP_DTYPE_F32                      h % 16 == 0, w % 32 == 0
+ *     MP_DTYPE_F32_SPLIT                h % 32 == 0, w % 32 == 0
+ *   (tests/test_gpu_circuit_shapes.py runs each rule's accepted and rejected sizes)
  *   timesteps <= the length of the "contextual_circuit/rho" weight */
 int mp_hgru_circuit_fwd(mp_ctx* ctx, const float* x, const float* o0, int64_t n, int64_t h,
                         int64_t w, int64_t k, int timesteps, float* o_out, void* stream);
@@ -233,7 +239,9 @@ int mp_circuit_set_variant(mp_ctx* ctx, const mp_circuit_variant* variant);
  * i0 are read with MP_HIDDEN_GIVEN only, and i0 only by a variant that reads the previous I
  * (gru_gates unset with alternate / mely integration, or mely at all); i_out may be NULL.  variant:
  * the flags the context was finalized with (MP_ERR_STATE if they differ) and this call's rng fields.
- * Map sizes as for mp_hgru_circuit_fwd. */
+ * Map sizes: the per-dtype rules of mp_hgru_circuit_fwd (MP_DTYPE_F32_FFT: any h in [1, 64], w 32 or
+ * 64; MP_DTYPE_F32: h % 16 == 0, w % 32 == 0; MP_DTYPE_F32_SPLIT: h % 32 == 0, w % 32 == 0), and
+ * n * h * w <= 2^24. */
 int mp_hgru_circuit_fwd_var(mp_ctx* ctx, const float* x, const float* o0, const float* i0, int64_t n, int64_t h,
                             int64_t w, int64_t k, int timesteps, int hidden_init, const mp_circuit_variant* variant,
                             float* o_out, float* i_out, float* states_O, float* states_I, void* stream);
