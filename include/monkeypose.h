@@ -173,8 +173,16 @@ int mp_hgru_pose_fwd_taps(mp_ctx* ctx, const float* depth, int64_t n, int64_t h,
                           const float* o0, float* out, const mp_pose_taps* taps, void* stream);
 
 /* ContextualCircuit(X, timesteps, ...).build() -> O  (hgru_module.py:872-959), hgru_pose aux:
- *   x, o0, o_out  [n, h, w, k] NHWC; k must be 64;
- *   map size, by the dtype the context was finalized with (MP_ERR_SHAPE otherwise, before any launch):
+ *   x, o0, o_out  [n, h, w, k] NHWC.  k is a property of the context: mp_finalize_weights takes it
+ *   from "contextual_circuit/p_r" [S,S,k,k] (4 <= k <= 256; i_r / o_r [1,1,k,k], the vectors
+ *   [1,1,1,k]; anything else is MP_ERR_WEIGHT), mp_info "channels" returns it, and the k passed here
+ *   must equal it (MP_ERR_SHAPE) -- there is nothing to express about x beyond that.
+ *   k == 64 runs the 64-channel loops below.  Any other k runs the channel-general loop (DESIGN.md
+ *   3f: NHWC maps, the graph runtime's implicit-GEMM convs, the epilogue kernels of
+ *   k_circuit_nhwc.hip): MP_DTYPE_F32_SPLIT or MP_DTYPE_F32 only -- MP_DTYPE_F32_FFT and
+ *   MP_DTYPE_BF16 are MP_ERR_UNSUPPORTED at mp_finalize_weights, their spectral GEMM and map layouts
+ *   being 64 wide -- with any h, w >= 1 (n * h * w <= 2^24), the pose aux run as its variant.
+ *   map size at k == 64, by the dtype the context was finalized with (MP_ERR_SHAPE otherwise, before any launch):
  *     MP_DTYPE_F32_FFT, MP_DTYPE_BF16   any h in [1, 64] (rows past h are zero padding of the 72-point
  *                                       transforms), w == 32 or w == 64
  *     MP_DTYPE_F32                      h % 16 == 0, w % 32 == 0
@@ -233,6 +241,12 @@ typedef struct {
  * mp_hgru_circuit_fwd_var only; one without serves the fused entries only (MP_ERR_STATE otherwise). */
 int mp_circuit_set_variant(mp_ctx* ctx, const mp_circuit_variant* variant);
 
+/* enable != 0: a 64-channel MP_MODEL_HGRU_CIRCUIT context runs the channel-general loop too (for a
+ * cross-check of the two loops, and for map sizes the 64-channel tilings reject); before
+ * mp_finalize_weights, with or without a variant.  Off by default: k == 64 then takes the 64-channel
+ * loops exactly as before.  Contexts of any other k run that loop whatever this says. */
+int mp_circuit_set_nhwc_loop(mp_ctx* ctx, int enable);
+
 /* ContextualCircuit(X, timesteps, ..., aux).build() for the context's variant.  x, o0, i0, o_out,
  * i_out [n, h, w, 64] NHWC fp32; states_O / states_I [n, timesteps, h, w, 64] or NULL (every step's
  * O_t after the rho gain / I_t).  hidden_init as in mp_fwd_opts, for both states (875-892): o0 and
@@ -241,7 +255,8 @@ int mp_circuit_set_variant(mp_ctx* ctx, const mp_circuit_variant* variant);
  * the flags the context was finalized with (MP_ERR_STATE if they differ) and this call's rng fields.
  * Map sizes: the per-dtype rules of mp_hgru_circuit_fwd (MP_DTYPE_F32_FFT: any h in [1, 64], w 32 or
  * 64; MP_DTYPE_F32: h % 16 == 0, w % 32 == 0; MP_DTYPE_F32_SPLIT: h % 32 == 0, w % 32 == 0), and
- * n * h * w <= 2^24. */
+ * n * h * w <= 2^24.  On the channel-general loop (k != 64, or mp_circuit_set_nhwc_loop) every 64
+ * above is the context's k and any h, w >= 1 is taken. */
 int mp_hgru_circuit_fwd_var(mp_ctx* ctx, const float* x, const float* o0, const float* i0, int64_t n, int64_t h,
                             int64_t w, int64_t k, int timesteps, int hidden_init, const mp_circuit_variant* variant,
                             float* o_out, float* i_out, float* states_O, float* states_I, void* stream);
@@ -477,7 +492,8 @@ int mp_eval_summary_dev(const void* state, int64_t joints, int64_t T, double* ou
 
 /* read a model property: "output_shape", "timesteps", "ssf", "finalized", "workspace_bytes",
  * "weight_bytes", "fft_loop" (hGRU contexts: 4 = the four-step FFT loop, 6 = the six-launch FFT
- * loop, 0 = a direct-convolution dtype, no FFT path); graph contexts also "graph_kernels" (kernel launches per forward),
+ * loop, 0 = a direct-convolution dtype, no FFT path), "channels" (the circuit's channel count k, from
+ * p_r at mp_finalize_weights), "nhwc_loop" (1: finalized for the channel-general loop); graph contexts also "graph_kernels" (kernel launches per forward),
  * "graph_streams" (streams the schedule uses), "graph_buffers" (activation buffers after concat placement), "graph_fused_pools" (2x2 max pools
  * computed inside their conv's kernel: MP_GRAPH_FUSE / MP_GRAPH_FUSE_POOL), "graph_fused_1x1" (1x1
  * convs computed by a sibling's kernel) and "graph_path:<conv layer scope>" (the kernel the planned

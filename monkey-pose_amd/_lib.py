@@ -34,10 +34,20 @@ DTYPES = {'fp32': MP_DTYPE_F32, 'f32': MP_DTYPE_F32, 'fp32_split': MP_DTYPE_F32_
           'bf16': MP_DTYPE_BF16}
 
 
-def resolve_dtype(name: str, h: int, w: int) -> str:
+def resolve_dtype(name: str, h: int, w: int, k: int = 64, nhwc_loop: bool = False) -> str:
     """'auto' -> the fastest fp32-class eCRF path supporting an h x w hGRU map: the FFT path for
     maps up to 64 x 64 with width 32 or 64 (the reference's 128^2 / 64^2 crops), else the f16x3
-    direct path for multiples of 32, else exact fp32.  Explicit names pass through."""
+    direct path for multiples of 32, else exact fp32.  Explicit names pass through.
+
+    A circuit of k != 64 channels (or ``nhwc_loop``: 64 channels sent there) runs the channel-general
+    loop, any map size: 'auto' is 'fp32_split', 'fp32' passes, and the FFT path's dtypes raise -- its
+    spectral GEMM and map layouts are 64 channels wide."""
+    if k != 64 or nhwc_loop:
+        if name in ('fp32_fft', 'f32_fft', 'bf16'):
+            raise ValueError(f"compute dtype {name!r} runs on the FFT path, which is 64 channels wide: a "
+                             f"{k}-channel circuit{' on the channel-general loop' if k == 64 else ''} runs "
+                             "'fp32_split' or 'fp32'")
+        return 'fp32_split' if name == 'auto' else name
     if name == 'bf16' and not (1 <= h <= 64 and w in (32, 64)):
         raise ValueError("compute dtype 'bf16' runs on the FFT path: hGRU map height <= 64, width 32 or 64")
     if name != 'auto':
@@ -87,6 +97,7 @@ _SIGS = {
                                                 ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
                                                 ctypes.c_void_p, ctypes.c_void_p]),
     "mp_circuit_set_variant": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "mp_circuit_set_nhwc_loop": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "mp_hgru_circuit_fwd_var": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
@@ -324,6 +335,10 @@ class Context:
 
     def set_circuit_variant(self, variant: CircuitVariant) -> None:
         check(self.lib.mp_circuit_set_variant(self.h, ctypes.byref(variant)))
+
+    def set_nhwc_loop(self, enable: bool = True) -> None:
+        """a 64-channel circuit context takes the channel-general loop (before ``finalize``)"""
+        check(self.lib.mp_circuit_set_nhwc_loop(self.h, 1 if enable else 0))
 
     def circuit_fwd_var(self, x, o0, i0, out, i_out, timesteps: int, stream: int, variant: CircuitVariant,
                         hidden_init: int = 0, states_O=None, states_I=None) -> None:

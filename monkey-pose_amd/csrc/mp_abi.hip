@@ -90,9 +90,9 @@ void pack_x3(const RawWeight& w, DevBuf& out, int ks, float ascale, float* unsca
 
 // the vector table of a variant context (CV_VECS rows): a learned vector is the caller's weight, the
 // others the constants prepare_tensors gives them (hgru_module.py:404-497); rho only with adaptation
-void finalize_variant_vecs(mp_ctx* c) {
-  const mp_circuit_variant& m = c->var;
-  std::vector<float> v(CV_VECS * 64, 0.f);
+// (k: the channel count, 64 on every loop but the channel-general one)
+void finalize_variant_vecs(mp_ctx* c, const mp_circuit_variant& m, int k = 64) {
+  std::vector<float> v((size_t)CV_VECS * k, 0.f);
   auto put = [&](int row, const char* name, int bit, bool learned) {
     float cst = 1.f;
     if (m.lesion & bit) {
@@ -100,10 +100,10 @@ void finalize_variant_vecs(mp_ctx* c) {
       learned = false;
     }
     if (learned) {
-      auto x = vec64(c, name);
-      std::copy(x.begin(), x.end(), v.begin() + row * 64);
+      auto x = c->need(std::string("contextual_circuit/") + name, {1, 1, 1, k}).host;
+      std::copy(x.begin(), x.end(), v.begin() + row * k);
     } else {
-      std::fill(v.begin() + row * 64, v.begin() + (row + 1) * 64, cst);
+      std::fill(v.begin() + row * k, v.begin() + (row + 1) * k, cst);
     }
   };
   put(V_LAT, "lateral_bias", 0, true);
@@ -116,7 +116,7 @@ void finalize_variant_vecs(mp_ctx* c) {
   put(V_OMEGA, "omega", MP_CV_OMEGA, m.multiplicative_excitation != 0);
   put(CV_ZETA, "zeta", 0, (m.learned & MP_CV_ZETA) != 0);
   put(CV_XI, "xi", 0, (m.learned & MP_CV_XI) != 0);
-  std::fill(v.begin() + V_OUTS * 64, v.begin() + (V_OUTS + 1) * 64, 1.f);
+  std::fill(v.begin() + V_OUTS * k, v.begin() + (V_OUTS + 1) * k, 1.f);
   upload(c->vecs, v);
   c->rho.clear();
   c->timesteps = 0;
@@ -129,16 +129,70 @@ void finalize_variant_vecs(mp_ctx* c) {
   }
 }
 
+// the aux of hgru_pose (hgru_pose.py:20-39 over hgru_module.py:9-51) as a variant: what a context
+// without mp_circuit_set_variant computes
+mp_circuit_variant pose_variant() {
+  mp_circuit_variant m{};
+  m.struct_size = sizeof(m);
+  m.gru_gates = 1;
+  m.multiplicative_excitation = 1;
+  m.adaptation = 1;
+  m.recurrent_nl = MP_NL_TANH;
+  m.integration = MP_INT_ALTERNATE;
+  m.learned = MP_CV_BETA | MP_CV_NU | MP_CV_GAMMA;
+  return m;
+}
+
+mpcv::CircuitVariant pod_variant(const mp_circuit_variant& m);
+
+// the channel-general loop's weights (k from p_r): p_r, i_r and o_r as [K][k] implicit-GEMM matrices of
+// the graph runtime's launchers (f16x3 under MP_DTYPE_F32_SPLIT, exact fp32 under MP_DTYPE_F32), the
+// [CV_VECS][k] table, and k zeros for the association-field conv's bias
+void finalize_circuit_nhwc(mp_ctx* c, const RawWeight& p_r) {
+  const int k = c->chan;
+  if (c->dtype != MP_DTYPE_F32 && c->dtype != MP_DTYPE_F32_SPLIT)
+    fail(MP_ERR_UNSUPPORTED,
+         "a " + std::to_string(k) + "-channel circuit" + (k == 64 ? " on the channel-general loop" : "") +
+             " runs MP_DTYPE_F32_SPLIT or MP_DTYPE_F32: the FFT path's spectral GEMM and map layouts "
+             "(MP_DTYPE_F32_FFT, MP_DTYPE_BF16) are 64 channels wide");
+  const auto& i_r = c->need("contextual_circuit/i_r", {1, 1, k, k});
+  const auto& o_r = c->need("contextual_circuit/o_r", {1, 1, k, k});
+  auto pack = [&](mp_ctx::PackedLayer& L, const RawWeight& w, int ks) {
+    L.k = ks;
+    L.cin = L.cout = k;
+    L.K = ks * ks * k;
+    L.cinp = 0;
+    pack_matrix(c, L, w.dev->f(), true);
+  };
+  pack(c->cn_p, p_r, c->ssf);
+  pack(c->cn_ir, i_r, 1);
+  pack(c->cn_or, o_r, 1);
+  upload(c->cn_zero, std::vector<float>(k, 0.f));
+  const mp_circuit_variant m = c->has_var ? c->var : pose_variant();
+  c->cn_cv = pod_variant(m);
+  finalize_variant_vecs(c, m, k);
+}
+
 void finalize_circuit(mp_ctx* c, const std::vector<float>* outs, const std::vector<float>* outt) {
   if (c->has_var && c->dtype == MP_DTYPE_BF16)
     fail(MP_ERR_UNSUPPORTED, "circuit variants run MP_DTYPE_F32, _F32_SPLIT or _F32_FFT, not MP_DTYPE_BF16");
   auto it = c->raw.find("contextual_circuit/p_r");
   if (it == c->raw.end()) fail(MP_ERR_STATE, "weight not set: contextual_circuit/p_r");
   const auto& ps = it->second.shape;
-  if (ps.size() != 4 || ps[0] != ps[1] || ps[2] != 64 || ps[3] != 64 ||
-      !(ps[0] == 3 || ps[0] == 5 || ps[0] == 15))
-    fail(MP_ERR_WEIGHT, "contextual_circuit/p_r must be [S,S,64,64] with S in {3,5,15}");
+  // the standalone circuit takes its channel count from p_r (hgru_module.py:74, 107-116); the pose
+  // model's backbone is 64 wide
+  const bool any_k = c->model == MP_MODEL_HGRU_CIRCUIT;
+  if (ps.size() != 4 || ps[0] != ps[1] || ps[2] != ps[3] || !(ps[0] == 3 || ps[0] == 5 || ps[0] == 15) ||
+      (any_k ? ps[2] < CN_MIN_K || ps[2] > CN_MAX_K : ps[2] != 64))
+    fail(MP_ERR_WEIGHT, any_k ? "contextual_circuit/p_r must be [S,S,k,k] with S in {3,5,15} and k in [4, 256]"
+                              : "contextual_circuit/p_r must be [S,S,64,64] with S in {3,5,15}");
   c->ssf = (int)ps[0];
+  c->chan = (int)ps[2];
+  c->nhwc = any_k && (c->chan != 64 || c->nhwc_flag);
+  if (c->nhwc) {
+    finalize_circuit_nhwc(c, it->second);
+    return;
+  }
   c->p_pk.alloc((size_t)8 * c->ssf * c->ssf * 2 * 64 * 16);
   c->fft4 = false;
   if (c->dtype == MP_DTYPE_F32_SPLIT) {
@@ -173,7 +227,7 @@ void finalize_circuit(mp_ctx* c, const std::vector<float>* outs, const std::vect
       hip_check(pack_gate_x3(c->need("contextual_circuit/i_r", {1, 1, 64, 64}).dev->f(), c->ir_x3.p, &c->ir_us, false),
                 "pack i_r");
     }
-    finalize_variant_vecs(c);
+    finalize_variant_vecs(c, c->var);
     return;
   }
   std::vector<float> v(V_COUNT * 64);
@@ -689,13 +743,13 @@ void run_circuit(mp_ctx* c, int64_t n, int H, int W, int T, const float* o0_nhwc
 // MP_HIDDEN_GIVEN -> the caller's o0; ZEROS -> a zeroed workspace map; IDENTITY -> X (the
 // caller's NHWC x for the circuit, the C8 drive converted into a workspace map for the pose model)
 const float* hidden_state(mp_ctx* c, int hidden_init, const float* o0, const float* x_nhwc, int64_t n, int H, int W,
-                          hipStream_t st, uint64_t rng_seed = 0) {
-  const size_t bytes = (size_t)n * H * W * 64 * sizeof(float);
+                          hipStream_t st, uint64_t rng_seed = 0, int k = 64) {
+  const size_t bytes = (size_t)n * H * W * k * sizeof(float);
   switch (hidden_init) {
     case MP_HIDDEN_RANDOM:
       // a fresh xavier-uniform draw on the device (hgru_module.py:884-887), limit sqrt(6 / (k + k))
       c->h0.alloc(bytes);
-      hip_check(launch_hidden_uniform(c->h0.f(), (int64_t)n * H * W * 64, rng_seed, std::sqrt(6.0 / (2 * 64)), st),
+      hip_check(launch_hidden_uniform(c->h0.f(), (int64_t)n * H * W * k, rng_seed, std::sqrt(6.0 / (2 * k)), st),
                 "hidden_init random");
       return c->h0.f();
     case MP_HIDDEN_GIVEN:
@@ -810,6 +864,132 @@ void var_circuit(mp_ctx* c, int n, int H, int W, int T, const float* o0_nhwc, co
     store_step(so, c->O.f(), c->I.f(), 0, n, H, W, t, false, st);
   }
   if (i_out) hip_check(launch_c8_to_nhwc(c->I.f(), i_out, n, H, W, st), "final I");
+}
+
+// ---- the channel-general loop (contexts with c->nhwc: k != 64, or mp_circuit_set_nhwc_loop) ----
+// every map NHWC fp32 [n,h,w,k]; X is the caller's x itself.  Per timestep, on one stream:
+//   [g1p = O . i_r + i_b]        1x1 conv       gru_gates, or the variant blends I (blend_in)
+//   [A_in = O sigmoid(g1p)]      gate multiply  gru_gates
+//   P = p_r * (A_in | O)         conv
+//   I = rule_in(P, X, O, I, g1p) circuit_in
+//   [g2p = I . o_r + o_b]        1x1 conv       output_gru_gates, or the variant blends O (blend_out)
+//   [B_in = I sigmoid(g2p)]      gate multiply  output_gru_gates
+//   P = p_r * (B_in | I)         conv
+//   O = rule_out(P, I, O, g2p)   circuit_out    (the last step also writes the result)
+// 4 launches a step at the least (control integration), 7 for the pose aux, 8 at the most.  The convs
+// are the graph runtime's (k_igemm.hip), the other kernels k_circuit_nhwc.hip's; all of them compute a
+// pixel from its own image alone and in a fixed order, so outputs do not depend on the batch.
+
+// out = conv(src, L) + bias, SAME, stride 1, k -> k channels, in the context's precision
+void cn_conv(mp_ctx* c, const mp_ctx::PackedLayer& L, const float* src, const float* bias, float* dst, int n, int H,
+             int W, hipStream_t st, const char* what) {
+  ProfScope ps(c, st, L.k == 1 ? "cn_gate_conv" : "cn_conv");
+  IgemmArgs a{};
+  a.x = src;
+  a.ldx = L.cin;
+  a.N = n;
+  a.H = H;
+  a.W = W;
+  a.Cin = L.cin;
+  a.wpk = L.w.v4();
+  a.K = L.K;
+  a.bias = bias;
+  a.out = dst;
+  a.ldo = L.cout;
+  a.Cout = L.cout;
+  a.Ho = H;
+  a.Wo = W;
+  a.KS = L.k;
+  a.stride = 1;
+  a.pad_t = a.pad_l = L.k / 2;
+  a.nprod = L.nprod;
+  if (L.cinp) {   // the Cin-padded packing for the halo kernel (k_igemm.hip halo_geom)
+    a.wpad = L.wpad.p;
+    a.cinp = L.cinp;
+  }
+  hip_check(L.x3 ? launch_igemm_x3(a, L.w.p, L.wus, st) : launch_igemm_conv(a, st), what);
+}
+
+// per-step state outputs of NHWC maps: [batch][T][H][W][k]
+void cn_store_step(const StateOut* so, const float* O, const float* I, int n, size_t img, int t, hipStream_t st) {
+  if (!so) return;
+  const size_t row = img * sizeof(float), pitch = row * so->T;
+  if (so->O)
+    hip_check(hipMemcpy2DAsync(so->O + (size_t)t * img, pitch, O, row, row, n, hipMemcpyDeviceToDevice, st),
+              "store_states O");
+  if (so->I)
+    hip_check(hipMemcpy2DAsync(so->I + (size_t)t * img, pitch, I, row, row, n, hipMemcpyDeviceToDevice, st),
+              "store_states I");
+}
+
+void nhwc_circuit(mp_ctx* c, int n, int H, int W, int T, const float* x, const float* o0, const float* i0,
+                  float* o_out, float* i_out, const StateOut* so, hipStream_t st) {
+  const mpcv::CircuitVariant v = c->cn_cv;
+  const int k = c->chan;
+  const int64_t npix = (int64_t)n * H * W;
+  const size_t bytes = (size_t)npix * k * sizeof(float);
+  const bool g1 = v.gru_gates || v.blend_in, g2 = v.out_gates || v.blend_out;
+  c->O.alloc(bytes);
+  c->I.alloc(bytes);
+  c->specP.alloc(bytes);
+  if (v.gru_gates) c->Og.alloc(bytes);
+  if (v.out_gates) c->bufA.alloc(bytes);
+  if (g1 || g2) c->bufB.alloc(bytes);
+  float *O = c->O.f(), *I = c->I.f(), *P = c->specP.f(), *G = c->bufB.f();
+  const float* ib = c->vecs.f() + (size_t)V_IB * k;
+  const float* ob = c->vecs.f() + (size_t)V_OB * k;
+  hip_check(hipMemcpyAsync(O, o0, bytes, hipMemcpyDeviceToDevice, st), "O0");
+  if (mpcv::reads_prev_i(v)) hip_check(hipMemcpyAsync(I, i0, bytes, hipMemcpyDeviceToDevice, st), "I0");
+  CnArgs a{};
+  a.v = v;
+  a.P = P;
+  a.X = x;
+  a.O = O;
+  a.I = I;
+  a.G = G;
+  a.vecs = c->vecs.f();
+  a.k = k;
+  a.npix = npix;
+  for (int t = 0; t < T; ++t) {
+    const float* ain = O;
+    if (g1) cn_conv(c, c->cn_ir, O, ib, G, n, H, W, st, "input gate conv");
+    if (v.gru_gates) {   // A_in = O * sigmoid(O . i_r + i_b)        696-711
+      ProfScope ps(c, st, "cn_gate");
+      hip_check(launch_circuit_nhwc_gate(O, G, c->Og.f(), npix * k, st), "A_in");
+      ain = c->Og.f();
+    }
+    cn_conv(c, c->cn_p, ain, c->cn_zero.f(), P, n, H, W, st, "association-field conv (input half)");
+    {
+      ProfScope ps(c, st, "cn_in");
+      a.out = nullptr;
+      hip_check(launch_circuit_nhwc_in(a, st), "circuit input half");
+    }
+    const float* bin = I;
+    if (g2) cn_conv(c, c->cn_or, I, ob, G, n, H, W, st, "output gate conv");
+    if (v.out_gates) {   // B_in = I' * sigmoid(I' . o_r + o_b)        729-743
+      ProfScope ps(c, st, "cn_gate");
+      hip_check(launch_circuit_nhwc_gate(I, G, c->bufA.f(), npix * k, st), "B_in");
+      bin = c->bufA.f();
+    }
+    cn_conv(c, c->cn_p, bin, c->cn_zero.f(), P, n, H, W, st, "association-field conv (output half)");
+    {
+      ProfScope ps(c, st, "cn_out");
+      a.rho = v.adapt ? c->rho[t] : 1.f;
+      a.out = t == T - 1 ? o_out : nullptr;
+      hip_check(launch_circuit_nhwc_out(a, st), "circuit output half");
+    }
+    cn_store_step(so, O, I, n, (size_t)H * W * k, t, st);
+  }
+  if (i_out) hip_check(hipMemcpyAsync(i_out, I, bytes, hipMemcpyDeviceToDevice, st), "final I");
+}
+
+// the argument checks the channel-general entry points share (before any launch)
+void cn_check(mp_ctx* c, int64_t n, int64_t h, int64_t w, int64_t k, int timesteps) {
+  if (k != c->chan)
+    fail(MP_ERR_SHAPE, "channel count k must be " + std::to_string(c->chan) + ", the context's (from p_r)");
+  if (n <= 0 || h <= 0 || w <= 0 || n * h * w > (int64_t)1 << 24) fail(MP_ERR_SHAPE, "empty or oversized input");
+  if (timesteps < 1 || (c->cn_cv.adapt && timesteps > (int)c->rho.size()))
+    fail(MP_ERR_ARG, "timesteps must be at least 1 and, with adaptation, at most len(rho)");
 }
 
 }  // namespace
@@ -978,6 +1158,7 @@ int mp_reserve(mp_ctx* ctx, int64_t max_batch) {
     if (!ctx->finalized) fail(MP_ERR_STATE, "mp_reserve before mp_finalize_weights");
     hip_check(hipSetDevice(ctx->device), "hipSetDevice");
     if (ctx->model >= MP_MODEL_DENSE) return;   // regressors: sized at first call
+    if (ctx->nhwc) return;                      // the channel-general loop: sized at each call (grow-only)
     const int64_t hw = ctx->model == MP_MODEL_HGRU_POSE ? ctx->fc1_in / 64 : 64 * 64;
     ensure_ws(ctx, max_batch, hw, 1);
   });
@@ -1250,6 +1431,19 @@ int mp_hgru_circuit_fwd_opts(mp_ctx* ctx, const float* x, const float* o0, int64
     if (!ctx->finalized) fail(MP_ERR_STATE, "weights not finalized");
     if (ctx->has_var)
       fail(MP_ERR_STATE, "context finalized for a circuit variant: use mp_hgru_circuit_fwd_var");
+    if (ctx->nhwc) {   // the channel-general loop runs the pose aux as its variant
+      cn_check(ctx, n, h, w, k, timesteps);
+      hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+      hipStream_t st = static_cast<hipStream_t>(stream);
+      const float* h0 = hidden_state(ctx, hidden_init, o0, x, n, (int)h, (int)w, st, fo.rng_seed, (int)k);
+      StateOut so;
+      so.O = states_O;
+      so.I = states_I;
+      so.T = timesteps;
+      nhwc_circuit(ctx, (int)n, (int)h, (int)w, timesteps, x, h0, nullptr, o_out, nullptr,
+                   (states_O || states_I) ? &so : nullptr, st);
+      return;
+    }
     if (k != 64) fail(MP_ERR_SHAPE, "channel count k must be 64");
     if (n <= 0 || h <= 0 || w <= 0) fail(MP_ERR_SHAPE, "empty input");
     check_map(ctx, h, w, "x");
@@ -1286,6 +1480,18 @@ int mp_circuit_set_variant(mp_ctx* ctx, const mp_circuit_variant* variant) {
   });
 }
 
+int mp_circuit_set_nhwc_loop(mp_ctx* ctx, int enable) {
+  return guard([&] {
+    if (!ctx) fail(MP_ERR_ARG, "ctx is NULL");
+    if (ctx->model != MP_MODEL_HGRU_CIRCUIT)
+      fail(MP_ERR_STATE, "the channel-general loop runs on an MP_MODEL_HGRU_CIRCUIT context");
+    ctx->nhwc_flag = enable != 0;
+    ctx->finalized = false;
+    ctx->cap_batch = 0;   // the two loops size their workspaces differently
+    ctx->cap_hw = 0;
+  });
+}
+
 int mp_hgru_circuit_fwd_var(mp_ctx* ctx, const float* x, const float* o0, const float* i0, int64_t n, int64_t h,
                             int64_t w, int64_t k, int timesteps, int hidden_init, const mp_circuit_variant* variant,
                             float* o_out, float* i_out, float* states_O, float* states_I, void* stream) {
@@ -1298,19 +1504,26 @@ int mp_hgru_circuit_fwd_var(mp_ctx* ctx, const float* x, const float* o0, const 
     const bool live_i = mpcv::reads_prev_i(ctx->cv);
     if (hidden_init == MP_HIDDEN_GIVEN && (!o0 || (live_i && !i0)))
       fail(MP_ERR_ARG, "o0 / i0 is NULL (hidden_init = MP_HIDDEN_GIVEN)");
-    if (k != 64) fail(MP_ERR_SHAPE, "channel count k must be 64");
-    if (n <= 0 || h <= 0 || w <= 0 || n * h * w > (int64_t)1 << 24) fail(MP_ERR_SHAPE, "empty or oversized input");
-    check_map(ctx, h, w, "x");
-    if (timesteps < 1 || (ctx->cv.adapt && timesteps > (int)ctx->rho.size()))
-      fail(MP_ERR_ARG, "timesteps must be at least 1 and, with adaptation, at most len(rho)");
+    const bool cn = ctx->nhwc;   // the channel-general loop: k is the context's, any map size
+    if (cn) {
+      cn_check(ctx, n, h, w, k, timesteps);
+    } else {
+      if (k != 64) fail(MP_ERR_SHAPE, "channel count k must be 64");
+      if (n <= 0 || h <= 0 || w <= 0 || n * h * w > (int64_t)1 << 24) fail(MP_ERR_SHAPE, "empty or oversized input");
+      check_map(ctx, h, w, "x");
+      if (timesteps < 1 || (ctx->cv.adapt && timesteps > (int)ctx->rho.size()))
+        fail(MP_ERR_ARG, "timesteps must be at least 1 and, with adaptation, at most len(rho)");
+    }
     hip_check(hipSetDevice(ctx->device), "hipSetDevice");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    ensure_ws(ctx, n, h, w);
-    hip_check(launch_nhwc_to_c8(x, ctx->X.f(), (int)n, (int)h, (int)w, st), "nhwc_to_c8");
-    const float* h0 = hidden_state(ctx, hidden_init, o0, x, n, (int)h, (int)w, st, m.rng_seed + m.rng_call);
+    if (!cn) {
+      ensure_ws(ctx, n, h, w);
+      hip_check(launch_nhwc_to_c8(x, ctx->X.f(), (int)n, (int)h, (int)w, st), "nhwc_to_c8");
+    }
+    const float* h0 = hidden_state(ctx, hidden_init, o0, x, n, (int)h, (int)w, st, m.rng_seed + m.rng_call, (int)k);
     const float* hi = nullptr;
     if (live_i) {   // the initial I, made like O0 (hgru_module.py:875-892)
-      const size_t bytes = (size_t)n * h * w * 64 * sizeof(float);
+      const size_t bytes = (size_t)n * h * w * k * sizeof(float);
       switch (hidden_init) {
         case MP_HIDDEN_GIVEN: hi = i0; break;
         case MP_HIDDEN_IDENTITY: hi = x; break;
@@ -1321,8 +1534,8 @@ int mp_hgru_circuit_fwd_var(mp_ctx* ctx, const float* x, const float* o0, const 
           break;
         default:   // MP_HIDDEN_RANDOM (hidden_state checked the value): a second, independent draw
           ctx->i0.alloc(bytes);
-          hip_check(launch_hidden_uniform(ctx->i0.f(), n * h * w * 64, m.rng_seed_i + m.rng_call,
-                                          std::sqrt(6.0 / (2 * 64)), st),
+          hip_check(launch_hidden_uniform(ctx->i0.f(), n * h * w * k, m.rng_seed_i + m.rng_call,
+                                          std::sqrt(6.0 / (2 * k)), st),
                     "hidden_init random (I)");
           hi = ctx->i0.f();
       }
@@ -1331,8 +1544,11 @@ int mp_hgru_circuit_fwd_var(mp_ctx* ctx, const float* x, const float* o0, const 
     so.O = states_O;
     so.I = states_I;
     so.T = timesteps;
-    var_circuit(ctx, (int)n, (int)h, (int)w, timesteps, h0, hi, o_out, i_out, (states_O || states_I) ? &so : nullptr,
-                st);
+    const StateOut* sop = (states_O || states_I) ? &so : nullptr;
+    if (cn)
+      nhwc_circuit(ctx, (int)n, (int)h, (int)w, timesteps, x, h0, hi, o_out, i_out, sop, st);
+    else
+      var_circuit(ctx, (int)n, (int)h, (int)w, timesteps, h0, hi, o_out, i_out, sop, st);
   });
 }
 
@@ -1366,6 +1582,10 @@ int mp_info(mp_ctx* ctx, const char* key, int64_t* value) {
       *value = ctx->timesteps;
     else if (k == "ssf")
       *value = ctx->ssf;
+    else if (k == "channels")   // the circuit's channel count (from p_r; 64 before finalizing and for the pose model)
+      *value = ctx->chan;
+    else if (k == "nhwc_loop")   // 1: finalized for the channel-general loop
+      *value = ctx->nhwc ? 1 : 0;
     else if (k == "finalized")
       *value = ctx->finalized ? 1 : 0;
     else if (k == "fc1_in")

@@ -124,6 +124,26 @@ struct CvArgs {
 };
 hipError_t launch_circuit_in(const CvArgs& a, int B, hipStream_t st);
 hipError_t launch_circuit_out(const CvArgs& a, int B, hipStream_t st);
+// k_circuit_nhwc.hip: the epilogue kernels of the channel-general loop (any k; NHWC fp32 maps of
+// npix = n * h * w pixels).  The 1x1 gate products are convs of the caller's: G is their output
+constexpr int CN_MIN_K = 4, CN_MAX_K = 256;
+struct CnArgs {
+  mpcv::CircuitVariant v;
+  const float* P;        // the conv result before lateral_bias
+  const float* X;        // in: the drive
+  float* O;              // in: O (read);  out: O, updated in place to O'
+  float* I;              // in: the previous I, updated in place to I';  out: I' (read)
+  const float* G;        // in: g1p = O . i_r + i_b (blend_in);  out: g2p = I' . o_r + o_b (blend_out)
+  float* out;            // out, the last step: O_T (null on the other steps)
+  const float* vecs;     // [CV_VECS][k]
+  float rho;             // out: rho[t] (read with adapt)
+  int k;
+  int64_t npix;
+};
+hipError_t launch_circuit_nhwc_in(const CnArgs& a, hipStream_t st);
+hipError_t launch_circuit_nhwc_out(const CnArgs& a, hipStream_t st);
+// dst = src * sigmoid(gp) over total elements: the gated conv inputs A_in = O g1, B_in = I' g2
+hipError_t launch_circuit_nhwc_gate(const float* src, const float* gp, float* dst, int64_t total, hipStream_t st);
 // k_igemm.hip (dense / hierarchical regressors)
 struct IgemmArgs {
   const float* x;      // input view: pixel (n,y,x) channel ci at x[((n*H+y)*W+x)*ldx + cix + ci]

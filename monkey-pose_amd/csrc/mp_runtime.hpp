@@ -158,6 +158,14 @@ struct mp_ctx {
     DevBuf wpad;          // x3 convs with Cin % 32 != 0: the packing with Cin zero-padded to cinp per
     int cinp = 0;         // tap (the halo kernel's 32-channel chunks; same scale as w)
   };
+  // ---- the channel-general circuit loop (mp_abi.hip nhwc_circuit) ----
+  int chan = 64;            // k of contextual_circuit/p_r [S,S,k,k]
+  bool nhwc_flag = false;   // mp_circuit_set_nhwc_loop: a 64-channel circuit takes that loop too
+  bool nhwc = false;        // finalized for it: k != 64, or nhwc_flag
+  mpcv::CircuitVariant cn_cv{};         // the variant it runs (the pose aux without mp_circuit_set_variant)
+  PackedLayer cn_p, cn_ir, cn_or;       // p_r, i_r, o_r as [K][k] implicit-GEMM weights
+  DevBuf cn_zero;                       // k zeros: the bias of the association-field conv
+
   std::map<std::string, PackedLayer> layers;   // keyed by layer name ("conv_3_1", "p_fc_2", ...)
   std::map<std::string, DevBuf> ws;            // named activation buffers
   int64_t ws_batch = 0, ws_h = 0, ws_w = 0;

@@ -189,7 +189,7 @@ class ContextualCircuit(object):
 
     def build(self, weights: Optional[Dict[str, np.ndarray]] = None, h2_init=None,
               compute_dtype: str = 'auto', reference_stack_order: bool = False, h1_init=None,
-              general_loop: bool = False):
+              general_loop: bool = False, nhwc_loop: bool = False):
         """Run the circuit; returns ``(O, weights, activities)`` like the reference with
         ``return_weights=True`` (hgru_module.py:939-954).  ``compute_dtype``: 'auto' (the FFT
         path when the map allows), 'fp32_fft', 'fp32_split', 'fp32' or 'bf16' (see
@@ -210,20 +210,26 @@ class ContextualCircuit(object):
         ``reference_stacks``.)
 
         The pose aux runs the fused loop; any other aux, or ``general_loop=True``, the general loop,
-        which also returns the final I as ``weights['I']``."""
+        which also returns the final I as ``weights['I']``.
+
+        The channel count is X's: k = 64 runs those loops, any other k in [4, 256] the channel-general
+        loop ('fp32_split', which 'auto' then means, or 'fp32'; any map size), through
+        the same two entry points.  ``nhwc_loop=True`` sends a 64-channel circuit there too."""
         import torch
         X = self.X
         if not isinstance(X, torch.Tensor) or not X.is_cuda:
             raise TypeError("X must be a CUDA (ROCm) torch tensor [n, h, w, k]")
         if general_loop or not is_pose_aux(self.aux):
-            return self._build_general(weights, h2_init, h1_init, compute_dtype, reference_stack_order)
+            return self._build_general(weights, h2_init, h1_init, compute_dtype, reference_stack_order, nhwc_loop)
         if h1_init is not None:
             raise ValueError("h1_init is not read by the hgru_pose aux (gru_gates ignore the previous I)")
         wts = self.prepare_tensors(weights)
         ctx = _lib.Context(_lib.MP_MODEL_HGRU_CIRCUIT, X.device.index or 0)
         for name, val in wts.items():
             ctx.set_weight(name, val)
-        ctx.finalize(_lib.dtype_code(_lib.resolve_dtype(compute_dtype, X.shape[1], X.shape[2])))
+        if nhwc_loop:
+            ctx.set_nhwc_loop(True)
+        ctx.finalize(_lib.dtype_code(_lib.resolve_dtype(compute_dtype, X.shape[1], X.shape[2], self.k, nhwc_loop)))
         X = X.detach().float().contiguous()
         hidden = _lib.MP_HIDDEN[self.hidden_init]
         call = 0
@@ -258,11 +264,11 @@ class ContextualCircuit(object):
             return sO, weights_out, {}
         return O, weights_out, {}
 
-    def _build_general(self, weights, h2_init, h1_init, compute_dtype, reference_stack_order):
+    def _build_general(self, weights, h2_init, h1_init, compute_dtype, reference_stack_order, nhwc_loop=False):
         """``build`` through the general loop (mp_hgru_circuit_fwd_var)."""
         import torch
         X = self.X.detach().float().contiguous()
-        dtype = _lib.resolve_dtype(compute_dtype, X.shape[1], X.shape[2])
+        dtype = _lib.resolve_dtype(compute_dtype, X.shape[1], X.shape[2], self.k, nhwc_loop)
         if dtype == 'bf16':
             raise NotImplementedError("compute_dtype='bf16' runs the hgru_pose aux's fused loop only; the general "
                                       "loop runs 'fp32_fft', 'fp32_split' or 'fp32'")
@@ -288,6 +294,8 @@ class ContextualCircuit(object):
         variant = _lib.circuit_variant(self.aux, self.hidden_seed, self.hidden_seed_i, call)
         ctx = _lib.Context(_lib.MP_MODEL_HGRU_CIRCUIT, X.device.index or 0)
         ctx.set_circuit_variant(variant)
+        if nhwc_loop:
+            ctx.set_nhwc_loop(True)
         for name, val in wts.items():
             ctx.set_weight(name, val)
         ctx.finalize(_lib.dtype_code(dtype))
