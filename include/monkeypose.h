@@ -182,6 +182,10 @@ int mp_hgru_pose_fwd_taps(mp_ctx* ctx, const float* depth, int64_t n, int64_t h,
  *   k_circuit_nhwc.hip): MP_DTYPE_F32_SPLIT or MP_DTYPE_F32 only -- MP_DTYPE_F32_FFT and
  *   MP_DTYPE_BF16 are MP_ERR_UNSUPPORTED at mp_finalize_weights, their spectral GEMM and map layouts
  *   being 64 wide -- with any h, w >= 1 (n * h * w <= 2^24), the pose aux run as its variant.
+ *   With mp_circuit_set_nhwc_conv(MP_CN_CONV_FFT) that loop's association-field conv is an FFT conv
+ *   (DESIGN.md 3g): k % 4 == 0, MP_DTYPE_F32_SPLIT, every h, w in [1, 64] (a larger map is
+ *   MP_ERR_SHAPE before any launch, o_out untouched), and a conv input must keep
+ *   h * w * max|v| / 64 inside f16 range (65504) -- the limit of the 64-channel FFT path.
  *   map size at k == 64, by the dtype the context was finalized with (MP_ERR_SHAPE otherwise, before any launch):
  *     MP_DTYPE_F32_FFT, MP_DTYPE_BF16   any h in [1, 64] (rows past h are zero padding of the 72-point
  *                                       transforms), w == 32 or w == 64
@@ -247,6 +251,21 @@ int mp_circuit_set_variant(mp_ctx* ctx, const mp_circuit_variant* variant);
  * loops exactly as before.  Contexts of any other k run that loop whatever this says. */
 int mp_circuit_set_nhwc_loop(mp_ctx* ctx, int enable);
 
+/* the algorithm of the channel-general loop's association-field conv (the compute dtype keeps naming the
+ * arithmetic): MP_CN_CONV_DIRECT, the default, is the implicit-GEMM conv; MP_CN_CONV_FFT a forward FFT,
+ * an f16x3 spectral product per frequency and an inverse FFT on a 72 x 72 grid (k_circuit_fft.hip,
+ * DESIGN.md 3g).  Before mp_finalize_weights, with or without a variant; MP_ERR_STATE on a finalized
+ * context, MP_ERR_ARG for another value.  With MP_CN_CONV_FFT set, mp_finalize_weights is
+ * MP_ERR_UNSUPPORTED, before any launch, for a context that is not on the channel-general loop (k == 64
+ * without mp_circuit_set_nhwc_loop: 64 channels have MP_DTYPE_F32_FFT), for k % 4 != 0, and for any
+ * dtype but MP_DTYPE_F32_SPLIT; a call with h > 64 or w > 64 is MP_ERR_SHAPE.  Spectra are kept for at
+ * most mp_info "nhwc_fft_chunk" images at a time (S + Y within 1 GiB): a larger batch is walked in chunks,
+ * which changes no bit of any output.  Range: a conv input (O, I or their gated forms) must keep
+ * h * w * max|v| / 64 inside f16 range. */
+#define MP_CN_CONV_DIRECT 0
+#define MP_CN_CONV_FFT 1
+int mp_circuit_set_nhwc_conv(mp_ctx* ctx, int conv);
+
 /* ContextualCircuit(X, timesteps, ..., aux).build() for the context's variant.  x, o0, i0, o_out,
  * i_out [n, h, w, 64] NHWC fp32; states_O / states_I [n, timesteps, h, w, 64] or NULL (every step's
  * O_t after the rho gain / I_t).  hidden_init as in mp_fwd_opts, for both states (875-892): o0 and
@@ -256,7 +275,8 @@ int mp_circuit_set_nhwc_loop(mp_ctx* ctx, int enable);
  * Map sizes: the per-dtype rules of mp_hgru_circuit_fwd (MP_DTYPE_F32_FFT: any h in [1, 64], w 32 or
  * 64; MP_DTYPE_F32: h % 16 == 0, w % 32 == 0; MP_DTYPE_F32_SPLIT: h % 32 == 0, w % 32 == 0), and
  * n * h * w <= 2^24.  On the channel-general loop (k != 64, or mp_circuit_set_nhwc_loop) every 64
- * above is the context's k and any h, w >= 1 is taken. */
+ * above is the context's k and any h, w >= 1 is taken; with MP_CN_CONV_FFT (mp_circuit_set_nhwc_conv)
+ * h, w in [1, 64], and every conv input keeps h * w * max|v| / 64 inside f16 range. */
 int mp_hgru_circuit_fwd_var(mp_ctx* ctx, const float* x, const float* o0, const float* i0, int64_t n, int64_t h,
                             int64_t w, int64_t k, int timesteps, int hidden_init, const mp_circuit_variant* variant,
                             float* o_out, float* i_out, float* states_O, float* states_I, void* stream);
@@ -493,7 +513,9 @@ int mp_eval_summary_dev(const void* state, int64_t joints, int64_t T, double* ou
 /* read a model property: "output_shape", "timesteps", "ssf", "finalized", "workspace_bytes",
  * "weight_bytes", "fft_loop" (hGRU contexts: 4 = the four-step FFT loop, 6 = the six-launch FFT
  * loop, 0 = a direct-convolution dtype, no FFT path), "channels" (the circuit's channel count k, from
- * p_r at mp_finalize_weights), "nhwc_loop" (1: finalized for the channel-general loop); graph contexts also "graph_kernels" (kernel launches per forward),
+ * p_r at mp_finalize_weights), "nhwc_loop" (1: finalized for the channel-general loop),
+ * "nhwc_conv" (1: that loop's conv is the FFT conv, MP_CN_CONV_FFT), "nhwc_fft_chunk" (images per chunk of the
+ * FFT conv at the context's k); graph contexts also "graph_kernels" (kernel launches per forward),
  * "graph_streams" (streams the schedule uses), "graph_buffers" (activation buffers after concat placement), "graph_fused_pools" (2x2 max pools
  * computed inside their conv's kernel: MP_GRAPH_FUSE / MP_GRAPH_FUSE_POOL), "graph_fused_1x1" (1x1
  * convs computed by a sibling's kernel) and "graph_path:<conv layer scope>" (the kernel the planned

@@ -59,6 +59,38 @@ def resolve_dtype(name: str, h: int, w: int, k: int = 64, nhwc_loop: bool = Fals
     return 'fp32'
 
 
+MP_CN_CONV_DIRECT = 0
+MP_CN_CONV_FFT = 1
+NHWC_CONVS = {'direct': MP_CN_CONV_DIRECT, 'fft': MP_CN_CONV_FFT}
+NHWC_FFT_MAX_HW = 64
+
+
+def resolve_nhwc_conv(name: str, compute_dtype: str, h: int, w: int, k: int = 64, nhwc_loop: bool = False) -> int:
+    """The MP_CN_CONV_* code of the channel-general loop's association-field conv ('direct', the default,
+    or 'fft': mp_circuit_set_nhwc_conv), refusing before a context exists what mp_finalize_weights and
+    the forward call refuse: 'fft' is that loop's (k != 64, or ``nhwc_loop``), needs k % 4 == 0,
+    'fp32_split' arithmetic ('auto' means it there, and never picks 'fft' by itself) and an h x w map of
+    at most 64 x 64."""
+    if name not in NHWC_CONVS:
+        raise ValueError(f"nhwc_conv must be one of {sorted(NHWC_CONVS)}, got {name!r}")
+    if name == 'direct':
+        return MP_CN_CONV_DIRECT
+    if k == 64 and not nhwc_loop:
+        raise ValueError("nhwc_conv='fft' is the channel-general loop's conv: a 64-channel circuit off that loop "
+                         "(nhwc_loop=False) has compute_dtype='fp32_fft'")
+    if k % 4 != 0:
+        raise ValueError(f"nhwc_conv='fft' transforms 4-channel groups: k = {k} is no multiple of 4 "
+                         "(nhwc_conv='direct' runs any k)")
+    dtype = resolve_dtype(compute_dtype, h, w, k, nhwc_loop)        # 'fp32_fft' / 'bf16' raise here, naming k
+    if dtype_code(dtype) != MP_DTYPE_F32_SPLIT:
+        raise ValueError(f"nhwc_conv='fft' of a {k}-channel circuit runs compute_dtype='fp32_split' (an f16x3 "
+                         f"spectral product) only, got {compute_dtype!r}")
+    if not (1 <= h <= NHWC_FFT_MAX_HW and 1 <= w <= NHWC_FFT_MAX_HW):
+        raise ValueError(f"nhwc_conv='fft' takes maps up to 64 x 64 (a 72-point transform), got {h} x {w}: "
+                         "nhwc_conv='direct' runs any map size")
+    return MP_CN_CONV_FFT
+
+
 def dtype_code(name: str) -> int:
     if name not in DTYPES:
         raise ValueError(f"compute dtype must be one of {sorted(DTYPES)}, got {name!r}")
@@ -98,6 +130,7 @@ _SIGS = {
                                                 ctypes.c_void_p, ctypes.c_void_p]),
     "mp_circuit_set_variant": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "mp_circuit_set_nhwc_loop": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "mp_circuit_set_nhwc_conv": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "mp_hgru_circuit_fwd_var": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
@@ -339,6 +372,11 @@ class Context:
     def set_nhwc_loop(self, enable: bool = True) -> None:
         """a 64-channel circuit context takes the channel-general loop (before ``finalize``)"""
         check(self.lib.mp_circuit_set_nhwc_loop(self.h, 1 if enable else 0))
+
+    def set_nhwc_conv(self, conv: int) -> None:
+        """the channel-general loop's association-field conv: MP_CN_CONV_DIRECT or MP_CN_CONV_FFT (before
+        ``finalize``)"""
+        check(self.lib.mp_circuit_set_nhwc_conv(self.h, int(conv)))
 
     def circuit_fwd_var(self, x, o0, i0, out, i_out, timesteps: int, stream: int, variant: CircuitVariant,
                         hidden_init: int = 0, states_O=None, states_I=None) -> None:

@@ -155,6 +155,13 @@ void finalize_circuit_nhwc(mp_ctx* c, const RawWeight& p_r) {
          "a " + std::to_string(k) + "-channel circuit" + (k == 64 ? " on the channel-general loop" : "") +
              " runs MP_DTYPE_F32_SPLIT or MP_DTYPE_F32: the FFT path's spectral GEMM and map layouts "
              "(MP_DTYPE_F32_FFT, MP_DTYPE_BF16) are 64 channels wide");
+  const bool fft = c->cn_conv_mode == MP_CN_CONV_FFT;
+  if (fft && k % 4 != 0)
+    fail(MP_ERR_UNSUPPORTED, "MP_CN_CONV_FFT transforms 4-channel groups: k = " + std::to_string(k) +
+                                 " is no multiple of 4 (MP_CN_CONV_DIRECT runs any k)");
+  if (fft && c->dtype != MP_DTYPE_F32_SPLIT)
+    fail(MP_ERR_UNSUPPORTED, "MP_CN_CONV_FFT of a " + std::to_string(k) +
+                                 "-channel circuit runs MP_DTYPE_F32_SPLIT (an f16x3 spectral product) only");
   const auto& i_r = c->need("contextual_circuit/i_r", {1, 1, k, k});
   const auto& o_r = c->need("contextual_circuit/o_r", {1, 1, k, k});
   auto pack = [&](mp_ctx::PackedLayer& L, const RawWeight& w, int ks) {
@@ -164,13 +171,19 @@ void finalize_circuit_nhwc(mp_ctx* c, const RawWeight& p_r) {
     L.cinp = 0;
     pack_matrix(c, L, w.dev->f(), true);
   };
-  pack(c->cn_p, p_r, c->ssf);
+  if (fft) {   // the spectral weights take the direct conv's place
+    c->cn_fft_g.alloc(cnf_weight_bytes(k));
+    hip_check(build_cn_spec_weights(p_r.dev->f(), c->ssf, k, c->cn_fft_g.p, &c->cn_fft_us), "p_r spectrum");
+  } else {
+    pack(c->cn_p, p_r, c->ssf);
+  }
   pack(c->cn_ir, i_r, 1);
   pack(c->cn_or, o_r, 1);
   upload(c->cn_zero, std::vector<float>(k, 0.f));
   const mp_circuit_variant m = c->has_var ? c->var : pose_variant();
   c->cn_cv = pod_variant(m);
   finalize_variant_vecs(c, m, k);
+  c->cn_fft = fft;
 }
 
 void finalize_circuit(mp_ctx* c, const std::vector<float>* outs, const std::vector<float>* outt) {
@@ -189,6 +202,11 @@ void finalize_circuit(mp_ctx* c, const std::vector<float>* outs, const std::vect
   c->ssf = (int)ps[0];
   c->chan = (int)ps[2];
   c->nhwc = any_k && (c->chan != 64 || c->nhwc_flag);
+  c->cn_fft = false;
+  if (c->cn_conv_mode == MP_CN_CONV_FFT && !c->nhwc)
+    fail(MP_ERR_UNSUPPORTED,
+         "MP_CN_CONV_FFT is the channel-general loop's: a " + std::to_string(c->chan) +
+             "-channel circuit off that loop (no mp_circuit_set_nhwc_loop) has MP_DTYPE_F32_FFT");
   if (c->nhwc) {
     finalize_circuit_nhwc(c, it->second);
     return;
@@ -910,6 +928,32 @@ void cn_conv(mp_ctx* c, const mp_ctx::PackedLayer& L, const float* src, const fl
   hip_check(L.x3 ? launch_igemm_x3(a, L.w.p, L.wus, st) : launch_igemm_conv(a, st), what);
 }
 
+// dst = p_r * src (SAME, no bias) as forward FFT, spectral product, inverse FFT (k_circuit_fft.hip), the
+// batch walked in chunks of cnf_chunk(k) images so that S + Y stay within CNF_WS_BYTES; every kernel
+// computes an image from that image alone, so the chunking changes no bit of any output
+void cn_conv_fft(mp_ctx* c, const float* src, float* dst, int n, int H, int W, hipStream_t st, const char* what) {
+  const int k = c->chan, chunk = cnf_chunk(k);
+  const size_t spec = cnf_image_bytes(k) * (size_t)std::min(n, chunk);
+  c->specS.alloc(spec);
+  c->specY.alloc(spec);
+  for (int b0 = 0; b0 < n; b0 += chunk) {
+    const int nb = std::min(chunk, n - b0);
+    const size_t off = (size_t)b0 * H * W * k;
+    {
+      ProfScope ps(c, st, "cn_fft_fwd");
+      hip_check(launch_cn_fft_fwd(src + off, c->specS.p, nb, H, W, k, st), what);
+    }
+    {
+      ProfScope ps(c, st, "cn_spec_gemm");
+      hip_check(launch_cn_spec_gemm(c->specS.p, c->cn_fft_g.p, c->specY.p, nb, k, st), what);
+    }
+    {
+      ProfScope ps(c, st, "cn_fft_inv");
+      hip_check(launch_cn_fft_inv(c->specY.p, dst + off, nb, H, W, k, c->cn_fft_us, st), what);
+    }
+  }
+}
+
 // per-step state outputs of NHWC maps: [batch][T][H][W][k]
 void cn_store_step(const StateOut* so, const float* O, const float* I, int n, size_t img, int t, hipStream_t st) {
   if (!so) return;
@@ -958,7 +1002,10 @@ void nhwc_circuit(mp_ctx* c, int n, int H, int W, int T, const float* x, const f
       hip_check(launch_circuit_nhwc_gate(O, G, c->Og.f(), npix * k, st), "A_in");
       ain = c->Og.f();
     }
-    cn_conv(c, c->cn_p, ain, c->cn_zero.f(), P, n, H, W, st, "association-field conv (input half)");
+    if (c->cn_fft)
+      cn_conv_fft(c, ain, P, n, H, W, st, "association-field conv (input half)");
+    else
+      cn_conv(c, c->cn_p, ain, c->cn_zero.f(), P, n, H, W, st, "association-field conv (input half)");
     {
       ProfScope ps(c, st, "cn_in");
       a.out = nullptr;
@@ -971,7 +1018,10 @@ void nhwc_circuit(mp_ctx* c, int n, int H, int W, int T, const float* x, const f
       hip_check(launch_circuit_nhwc_gate(I, G, c->bufA.f(), npix * k, st), "B_in");
       bin = c->bufA.f();
     }
-    cn_conv(c, c->cn_p, bin, c->cn_zero.f(), P, n, H, W, st, "association-field conv (output half)");
+    if (c->cn_fft)
+      cn_conv_fft(c, bin, P, n, H, W, st, "association-field conv (output half)");
+    else
+      cn_conv(c, c->cn_p, bin, c->cn_zero.f(), P, n, H, W, st, "association-field conv (output half)");
     {
       ProfScope ps(c, st, "cn_out");
       a.rho = v.adapt ? c->rho[t] : 1.f;
@@ -988,6 +1038,9 @@ void cn_check(mp_ctx* c, int64_t n, int64_t h, int64_t w, int64_t k, int timeste
   if (k != c->chan)
     fail(MP_ERR_SHAPE, "channel count k must be " + std::to_string(c->chan) + ", the context's (from p_r)");
   if (n <= 0 || h <= 0 || w <= 0 || n * h * w > (int64_t)1 << 24) fail(MP_ERR_SHAPE, "empty or oversized input");
+  if (c->cn_fft && (h > CNF_MAX_HW || w > CNF_MAX_HW))
+    fail(MP_ERR_SHAPE, "MP_CN_CONV_FFT takes maps up to 64 x 64 (a 72-point transform), got " + std::to_string(h) +
+                           " x " + std::to_string(w) + ": MP_CN_CONV_DIRECT runs any map size");
   if (timesteps < 1 || (c->cn_cv.adapt && timesteps > (int)c->rho.size()))
     fail(MP_ERR_ARG, "timesteps must be at least 1 and, with adaptation, at most len(rho)");
 }
@@ -1492,6 +1545,18 @@ int mp_circuit_set_nhwc_loop(mp_ctx* ctx, int enable) {
   });
 }
 
+int mp_circuit_set_nhwc_conv(mp_ctx* ctx, int conv) {
+  return guard([&] {
+    if (!ctx) fail(MP_ERR_ARG, "ctx is NULL");
+    if (ctx->model != MP_MODEL_HGRU_CIRCUIT)
+      fail(MP_ERR_STATE, "the channel-general loop runs on an MP_MODEL_HGRU_CIRCUIT context");
+    if (ctx->finalized) fail(MP_ERR_STATE, "mp_circuit_set_nhwc_conv after mp_finalize_weights: set it before finalizing");
+    if (conv != MP_CN_CONV_DIRECT && conv != MP_CN_CONV_FFT)
+      fail(MP_ERR_ARG, "conv must be MP_CN_CONV_DIRECT or MP_CN_CONV_FFT, got " + std::to_string(conv));
+    ctx->cn_conv_mode = conv;
+  });
+}
+
 int mp_hgru_circuit_fwd_var(mp_ctx* ctx, const float* x, const float* o0, const float* i0, int64_t n, int64_t h,
                             int64_t w, int64_t k, int timesteps, int hidden_init, const mp_circuit_variant* variant,
                             float* o_out, float* i_out, float* states_O, float* states_I, void* stream) {
@@ -1586,6 +1651,10 @@ int mp_info(mp_ctx* ctx, const char* key, int64_t* value) {
       *value = ctx->chan;
     else if (k == "nhwc_loop")   // 1: finalized for the channel-general loop
       *value = ctx->nhwc ? 1 : 0;
+    else if (k == "nhwc_conv")   // 1: finalized with the FFT association-field conv (MP_CN_CONV_FFT)
+      *value = ctx->cn_fft ? 1 : 0;
+    else if (k == "nhwc_fft_chunk")   // images per chunk of that conv at this context's channel count
+      *value = cnf_chunk(ctx->chan);
     else if (k == "finalized")
       *value = ctx->finalized ? 1 : 0;
     else if (k == "fc1_in")

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/monkeypose.h"
+#include "circuit_fft.hpp"
 #include "mp_kernels.hpp"
 
 using namespace mp;
@@ -165,6 +166,10 @@ struct mp_ctx {
   mpcv::CircuitVariant cn_cv{};         // the variant it runs (the pose aux without mp_circuit_set_variant)
   PackedLayer cn_p, cn_ir, cn_or;       // p_r, i_r, o_r as [K][k] implicit-GEMM weights
   DevBuf cn_zero;                       // k zeros: the bias of the association-field conv
+  int cn_conv_mode = MP_CN_CONV_DIRECT; // mp_circuit_set_nhwc_conv: the association-field conv's algorithm
+  bool cn_fft = false;                  // finalized with MP_CN_CONV_FFT (k_circuit_fft.hip; S / Y in specS / specY)
+  DevBuf cn_fft_g;                      // its compact split spectral weights of p_r
+  float cn_fft_us = 1.f;                // 1 / (their scale * SPEC_SCALE)
 
   std::map<std::string, PackedLayer> layers;   // keyed by layer name ("conv_3_1", "p_fc_2", ...)
   std::map<std::string, DevBuf> ws;            // named activation buffers

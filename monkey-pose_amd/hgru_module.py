@@ -189,7 +189,7 @@ class ContextualCircuit(object):
 
     def build(self, weights: Optional[Dict[str, np.ndarray]] = None, h2_init=None,
               compute_dtype: str = 'auto', reference_stack_order: bool = False, h1_init=None,
-              general_loop: bool = False, nhwc_loop: bool = False):
+              general_loop: bool = False, nhwc_loop: bool = False, nhwc_conv: str = 'direct'):
         """Run the circuit; returns ``(O, weights, activities)`` like the reference with
         ``return_weights=True`` (hgru_module.py:939-954).  ``compute_dtype``: 'auto' (the FFT
         path when the map allows), 'fp32_fft', 'fp32_split', 'fp32' or 'bf16' (see
@@ -214,13 +214,18 @@ class ContextualCircuit(object):
 
         The channel count is X's: k = 64 runs those loops, any other k in [4, 256] the channel-general
         loop ('fp32_split', which 'auto' then means, or 'fp32'; any map size), through
-        the same two entry points.  ``nhwc_loop=True`` sends a 64-channel circuit there too."""
+        the same two entry points.  ``nhwc_loop=True`` sends a 64-channel circuit there too.
+        ``nhwc_conv='fft'`` runs that loop's association-field conv as an FFT conv (k % 4 == 0,
+        'fp32_split', maps up to 64 x 64, conv inputs with h * w * max|v| / 64 inside f16 range; see
+        _lib.resolve_nhwc_conv); 'direct', the default, is the implicit-GEMM conv.  'auto' never picks 'fft':
+        at ssf 3 and 5 the direct conv is the faster one (README)."""
         import torch
         X = self.X
         if not isinstance(X, torch.Tensor) or not X.is_cuda:
             raise TypeError("X must be a CUDA (ROCm) torch tensor [n, h, w, k]")
+        conv = _lib.resolve_nhwc_conv(nhwc_conv, compute_dtype, X.shape[1], X.shape[2], self.k, nhwc_loop)
         if general_loop or not is_pose_aux(self.aux):
-            return self._build_general(weights, h2_init, h1_init, compute_dtype, reference_stack_order, nhwc_loop)
+            return self._build_general(weights, h2_init, h1_init, compute_dtype, reference_stack_order, nhwc_loop, conv)
         if h1_init is not None:
             raise ValueError("h1_init is not read by the hgru_pose aux (gru_gates ignore the previous I)")
         wts = self.prepare_tensors(weights)
@@ -229,6 +234,8 @@ class ContextualCircuit(object):
             ctx.set_weight(name, val)
         if nhwc_loop:
             ctx.set_nhwc_loop(True)
+        if conv != _lib.MP_CN_CONV_DIRECT:
+            ctx.set_nhwc_conv(conv)
         ctx.finalize(_lib.dtype_code(_lib.resolve_dtype(compute_dtype, X.shape[1], X.shape[2], self.k, nhwc_loop)))
         X = X.detach().float().contiguous()
         hidden = _lib.MP_HIDDEN[self.hidden_init]
@@ -264,7 +271,8 @@ class ContextualCircuit(object):
             return sO, weights_out, {}
         return O, weights_out, {}
 
-    def _build_general(self, weights, h2_init, h1_init, compute_dtype, reference_stack_order, nhwc_loop=False):
+    def _build_general(self, weights, h2_init, h1_init, compute_dtype, reference_stack_order, nhwc_loop=False,
+                       nhwc_conv=_lib.MP_CN_CONV_DIRECT):
         """``build`` through the general loop (mp_hgru_circuit_fwd_var)."""
         import torch
         X = self.X.detach().float().contiguous()
@@ -296,6 +304,8 @@ class ContextualCircuit(object):
         ctx.set_circuit_variant(variant)
         if nhwc_loop:
             ctx.set_nhwc_loop(True)
+        if nhwc_conv != _lib.MP_CN_CONV_DIRECT:
+            ctx.set_nhwc_conv(nhwc_conv)
         for name, val in wts.items():
             ctx.set_weight(name, val)
         ctx.finalize(_lib.dtype_code(dtype))

@@ -7,7 +7,7 @@ import subprocess
 import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "monkey-pose_amd", "csrc")
-SOURCES = ["k_fft.hip", "k_fc.hip", "k_igemm.hip", "k_conv64x3.hip", "k_conv64.hip", "k_frame.hip"]
+SOURCES = ["k_fft.hip", "k_circuit_fft.hip", "k_fc.hip", "k_igemm.hip", "k_conv64x3.hip", "k_conv64.hip", "k_frame.hip"]
 FIELDS = ["VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "LDS Size [bytes/block]"]
 
 
@@ -20,7 +20,7 @@ def demangle(names):
 def main():
     rows = []
     for src in SOURCES:
-        extra = ["-fno-slp-vectorize"] if src == "k_fft.hip" else []
+        extra = ["-fno-slp-vectorize"] if src in ("k_fft.hip", "k_circuit_fft.hip") else []
         cmd = ["/opt/rocm/bin/hipcc", *extra, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c",
                os.path.join(CSRC, src), "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"]
         err = subprocess.run(cmd, capture_output=True, text=True).stderr

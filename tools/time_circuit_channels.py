@@ -4,14 +4,19 @@ process, for the hgru_pose aux and the module's default aux (both through mp_hgr
   k32, k128     32 and 128 channels on the channel-general loop
   k64_nhwc      64 channels on the channel-general loop (mp_circuit_set_nhwc_loop)
   k64_general   64 channels on the general loop (k_conv64x3.hip + k_circuit_var.hip): the reference time
+  k32_fft, k64_nhwc_fft, k128_fft   the same contexts with the FFT association-field conv
+                (mp_circuit_set_nhwc_conv MP_CN_CONV_FFT, k_circuit_fft.hip)
+  k64_general_fft   64 channels on the general loop's fp32_fft (k_fft.hip)
 
 Device events around one forward, warm-up, then the median of --runs forwards per form, the forms
 alternating in rounds so that drift of a shared host hits all of them alike.  A second pass with the
 library's per-launch event profile on gives, for k = 32, 64 and 128 on the new loop, the time of the two
 epilogue kernels (cn_in / cn_out), of the gate multiply (cn_gate) and of the convs (cn_conv,
-cn_gate_conv) and the convs' share of the forward; each epilogue kernel's algorithmic bytes (maps read
-+ written, from the variant and the shapes) over its time is stated as a fraction of mp_hbm_probe's
-copy rate taken in the same process.  One JSON goes to profiles/channels/, stamped with
+cn_gate_conv; cn_fft_fwd, cn_spec_gemm, cn_fft_inv on the FFT forms) and the convs' share of the forward;
+each epilogue kernel's algorithmic bytes (maps read + written, from the variant and the shapes) and each
+FFT-conv kernel's (map + spectrum for the transforms, S + Y + weights for the product) over its time is
+stated as a fraction of mp_hbm_probe's copy rate taken in the same process.  --forms limits the run to
+some forms (ssf 3 and 5 are timed at k = 64 only).  One JSON goes to profiles/channels/, stamped with
 bench.tree_stamp.
 
     python tools/time_circuit_channels.py [--runs 10] [--batch 64] [--out profiles/channels/time_channels.json]
@@ -30,8 +35,28 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 AUX = {"pose": {'gru_gates': True, 'adapation': True}, "defaults": {}}
-FORMS = (("k32", 32, True), ("k128", 128, True), ("k64_nhwc", 64, True), ("k64_general", 64, False))
-PROFILE_KEYS = ("cn_in", "cn_out", "cn_gate", "cn_conv", "cn_gate_conv")
+# name, k, on the channel-general loop, its conv ('direct' / 'fft'), compute dtype
+FORMS = (("k32", 32, True, "direct", "fp32_split"), ("k32_fft", 32, True, "fft", "fp32_split"),
+         ("k128", 128, True, "direct", "fp32_split"), ("k128_fft", 128, True, "fft", "fp32_split"),
+         ("k64_nhwc", 64, True, "direct", "fp32_split"), ("k64_nhwc_fft", 64, True, "fft", "fp32_split"),
+         ("k64_general", 64, False, "direct", "fp32_split"), ("k64_general_fft", 64, False, "direct", "fp32_fft"))
+PROFILE_KEYS = ("cn_in", "cn_out", "cn_gate", "cn_conv", "cn_gate_conv", "cn_fft_fwd", "cn_spec_gemm", "cn_fft_inv")
+CONV_KEYS = ("cn_conv", "cn_gate_conv", "cn_fft_fwd", "cn_spec_gemm", "cn_fft_inv")
+NF = 72 * 37
+
+
+def fft_conv_bytes(n, h, w, k, T):
+    """algorithmic bytes of the 2 T launches of each FFT-conv kernel in one forward (circuit_fft.hpp): the
+    map and one spectrum for a transform; S, Y and the compact weights for the product"""
+    m = n * h * w * k * 4
+    spec = n * (k // 4) * NF * 32
+    wts = NF * 2 * ((k // 4 + 1) // 2 * 2) * ((k + 31) // 32 * 32) * 16
+    return {"cn_fft_fwd": 2 * T * (m + spec), "cn_fft_inv": 2 * T * (m + spec), "cn_spec_gemm": 2 * T * (2 * spec + wts)}
+
+
+def fft_conv_flops(n, k, T):
+    """real flops of the spectral product's 2 T launches as issued: 3 products (f16x3) of 2k x 2k x n per frequency"""
+    return 2 * T * 3 * 2 * (2 * k) * (2 * k) * n * NF
 
 
 def kernel_bytes(aux, n, h, w, k, T):
@@ -54,6 +79,7 @@ def main():
     ap.add_argument("--ssf", type=int, default=15)
     ap.add_argument("--timesteps", type=int, default=8)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "channels", "time_channels.json"))
+    ap.add_argument("--forms", default="", help="comma-separated form names (default: all)")
     ap.add_argument("--kernels-only", action="store_true")
     a = ap.parse_args()
     import torch
@@ -64,13 +90,14 @@ def main():
     dev = torch.device("cuda", 0)
     st = L.current_stream(dev)
     bufs = {}
-    for k in sorted({f[1] for f in FORMS}):
+    chosen = [f for f in FORMS if not a.forms or f[0] in a.forms.split(",")]
+    for k in sorted({f[1] for f in chosen}):
         x = torch.from_numpy(W.synth_hidden((n, hw, hw, k), seed=3, name="X", limit=1.0)).to(dev)
         o0 = torch.from_numpy(W.synth_hidden((n, hw, hw, k), seed=7)).to(dev)
         i0 = torch.from_numpy(W.synth_hidden((n, hw, hw, k), seed=1007)).to(dev)
         bufs[k] = (x, o0, i0, torch.empty_like(x), torch.empty_like(x))
 
-    def context(aux_name, k, nhwc):
+    def context(aux_name, k, nhwc, conv, dtype):
         aux = M.merged_aux(AUX[aux_name])
         table = W.hgru_circuit_vars(k=k, ssf=a.ssf, timesteps=T, scope="contextual_circuit", **M.variable_flags(aux))
         ctx = L.Context(L.MP_MODEL_HGRU_CIRCUIT, 0)
@@ -78,14 +105,18 @@ def main():
         ctx.set_circuit_variant(var)
         if nhwc and k == 64:
             ctx.set_nhwc_loop(True)
+        if conv == "fft":
+            ctx.set_nhwc_conv(L.MP_CN_CONV_FFT)
         for v in table:
             ctx.set_weight(v.name, W.synth_value(v, 1234, T))
-        ctx.finalize(L.MP_DTYPE_F32_SPLIT)
+        ctx.finalize(L.dtype_code(dtype))
         assert ctx.info("channels") == k and ctx.info("nhwc_loop") == int(nhwc)
+        assert ctx.info("nhwc_conv") == int(conv == "fft")
         x, o0, i0, out, iout = bufs[k]
         return ctx, aux, lambda: ctx.circuit_fwd_var(x, o0, i0, out, iout, T, st, var)
 
-    forms = {f"{an}/{name}": context(an, k, nhwc) + (k, nhwc) for an in AUX for name, k, nhwc in FORMS}
+    forms = {f"{an}/{name}": context(an, k, nhwc, conv, dtype) + (k, nhwc)
+             for an in AUX for name, k, nhwc, conv, dtype in chosen}
     if a.kernels_only:
         for name, f in forms.items():
             if f[4]:
@@ -107,21 +138,26 @@ def main():
             e1.record()
             e1.synchronize()
             times[k].append(e0.elapsed_time(e1))
-    res = {"tree": bench.tree_stamp(), "batch": n, "hw": [hw, hw], "ssf": a.ssf, "timesteps": T, "dtype": "fp32_split",
+    res = {"tree": bench.tree_stamp(), "batch": n, "hw": [hw, hw], "ssf": a.ssf, "timesteps": T,
+           "dtype": {f[0]: f[4] for f in chosen},
            "runs": a.runs, "warmup": a.warmup, "device": torch.cuda.get_device_name(0), "forward_ms": {}}
     for k, ts in times.items():
         res["forward_ms"][k] = {"p50": round(float(np.median(ts)), 4), "min": round(min(ts), 4),
                                 "max": round(max(ts), 4)}
     # the two loops' 64-channel outputs against each other (same inputs): the fp32-class gate's scale
-    res["k64_nhwc_vs_general_rel_inf"] = {}
+    res["k64_vs_general_rel_inf"] = {}
     for an in AUX:
+        if f"{an}/k64_general" not in forms:
+            continue
         out = bufs[64][3]
         forms[f"{an}/k64_general"][2]()
         torch.cuda.synchronize()
         ref = out.clone()
-        forms[f"{an}/k64_nhwc"][2]()
-        torch.cuda.synchronize()
-        res["k64_nhwc_vs_general_rel_inf"][an] = float((out - ref).abs().max() / ref.abs().max())
+        for other in ("k64_nhwc", "k64_nhwc_fft", "k64_general_fft"):
+            if f"{an}/{other}" in forms:
+                forms[f"{an}/{other}"][2]()
+                torch.cuda.synchronize()
+                res["k64_vs_general_rel_inf"][f"{an}/{other}"] = float((out - ref).abs().max() / ref.abs().max())
     # per-kernel times from the library's event profile (a pass of its own: the events serialise launches)
     probe = L.hbm_probe(0)
     res["hbm_probe"] = probe
@@ -144,11 +180,15 @@ def main():
         total = sum(fwd.values())
         kk = {"launches_per_forward": cnts, "ms_per_forward": {key: round(v, 4) for key, v in fwd.items()},
               "profiled_forward_ms": round(total, 4),
-              "conv_share_of_forward": round((fwd["cn_conv"] + fwd["cn_gate_conv"]) / total, 4)}
+              "conv_share_of_forward": round(sum(fwd[key] for key in CONV_KEYS) / total, 4)}
         b_in, b_out = kernel_bytes(aux, n, hw, hw, k, T)
-        for key, nbytes in (("cn_in", b_in), ("cn_out", b_out)):
+        rated = [("cn_in", b_in, T), ("cn_out", b_out, T)]
+        if fwd["cn_spec_gemm"] > 0:
+            rated += [(key, nb, 2 * T) for key, nb in fft_conv_bytes(n, hw, hw, k, T).items()]
+            kk["cn_spec_gemm_TFLOPs_issued"] = round(fft_conv_flops(n, k, T) / (fwd["cn_spec_gemm"] * 1e-3) / 1e12, 2)
+        for key, nbytes, launches in rated:
             gbps = nbytes / (fwd[key] * 1e-3) / 1e9
-            kk[key] = {"ms_per_launch_p50": round(fwd[key] / T, 4), "algorithmic_bytes_per_forward": nbytes,
+            kk[key] = {"ms_per_launch_p50": round(fwd[key] / launches, 4), "algorithmic_bytes_per_forward": nbytes,
                        "GBps": round(gbps, 1), "fraction_of_probe_copy": round(gbps / probe["copy_GBps"], 3)}
         res["kernels"][name] = kk
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
