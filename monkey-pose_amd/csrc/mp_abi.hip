@@ -286,6 +286,14 @@ void finalize_pose(mp_ctx* c) {
     c->conv3_pk.alloc((size_t)8 * 9 * 2 * 64 * 16);
     pack_x3(c->need("conv_2/conv_2_filters", {3, 3, k, k}), c->conv2_pk, 3, BB_ASCALE, &c->conv2_us, "pack conv_2");
     pack_x3(c->need("conv_3/conv_3_filters", {3, 3, k, k}), c->conv3_pk, 3, BB_ASCALE, &c->conv3_us, "pack conv_3");
+    // a map height the 32-row f16x3 tiles do not divide runs conv64_kernel (pose_fwd), which reads
+    // the exact-fp32 fragment packing, not the f16x3 one
+    c->conv2_pk32.alloc((size_t)8 * 9 * 2 * 64 * 16);
+    c->conv3_pk32.alloc((size_t)8 * 9 * 2 * 64 * 16);
+    hip_check(launch_pack_conv64(c->need("conv_2/conv_2_filters", {3, 3, k, k}).dev->f(), c->conv2_pk32.v4(), 3, nullptr),
+              "pack conv_2 (fp32)");
+    hip_check(launch_pack_conv64(c->need("conv_3/conv_3_filters", {3, 3, k, k}).dev->f(), c->conv3_pk32.v4(), 3, nullptr),
+              "pack conv_3 (fp32)");
   }
   copy_dev(c->conv2_b, c->need("conv_2/conv_2_biases", {k}));
   copy_dev(c->conv3_b, c->need("conv_3/conv_3_biases", {k}));
@@ -1310,7 +1318,9 @@ int pose_fwd(mp_ctx* ctx, const float* depth, int64_t n, int64_t h, int64_t w, c
       a.H = H;
       a.W = W;
       a.src = bA;
-      a.wpk = ctx->conv2_pk.v4();
+      // conv64_kernel's weights: the context's own packing under F32, else the fp32 copy kept beside the f16x3 one
+      const bool f32w = ctx->dtype == MP_DTYPE_F32;
+      a.wpk = f32w ? ctx->conv2_pk.v4() : ctx->conv2_pk32.v4();
       a.dst = bB;
       a.bias = ctx->conv2_b.f();
       a.bn_s = ctx->bn1_s.f();
@@ -1320,7 +1330,7 @@ int pose_fwd(mp_ctx* ctx, const float* depth, int64_t n, int64_t h, int64_t w, c
                    : launch_conv64(3, EPI_BB, a, cnt, s),
                 "conv_2");
       a.src = bB;
-      a.wpk = ctx->conv3_pk.v4();
+      a.wpk = f32w ? ctx->conv3_pk.v4() : ctx->conv3_pk32.v4();
       a.dst = xm;
       a.dst_bf16 = bf16_maps(ctx) ? 1 : 0;
       a.dst_c4 = x_c4(ctx) ? 1 : 0;

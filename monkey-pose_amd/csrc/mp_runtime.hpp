@@ -127,6 +127,7 @@ struct mp_ctx {
   DevBuf conv2_pk, conv2_b, bn1_s, bn1_t;
   float conv2_us = 1.f, conv3_us = 1.f;   // backbone packed f16x3 (dtype != F32): 1 / (wscale * BB_ASCALE)
   DevBuf conv3_pk, conv3_b, bn2_s, bn2_t;
+  DevBuf conv2_pk32, conv3_pk32;   // dtype != F32: the exact-fp32 packing too, for maps the f16x3 tiles do not divide
   DevBuf p_pk, ir_pk, or_pk, vecs;
   DevBuf spec_g;            // MP_DTYPE_F32_FFT: compact split spectral weights of p_r (k_fft.hip)
   bool fft4 = false;        // the fp32 FFT path runs k_fft4.hip's four-step loop (class-major spec_g)
