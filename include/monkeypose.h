@@ -186,6 +186,8 @@ int mp_hgru_pose_fwd_taps(mp_ctx* ctx, const float* depth, int64_t n, int64_t h,
  *   (DESIGN.md 3g): k % 4 == 0, MP_DTYPE_F32_SPLIT, every h, w in [1, 64] (a larger map is
  *   MP_ERR_SHAPE before any launch, o_out untouched), and a conv input must keep
  *   h * w * max|v| / 64 inside f16 range (65504) -- the limit of the 64-channel FFT path.
+ *   MP_CN_CONV_FFT_TILED is that conv on maps of any size (every h, w >= 1, n * h * w <= 2^24), cut
+ *   into 64 x 64 windows: the range bound is per window, min(h, 64) * min(w, 64) * max|v| / 64.
  *   map size at k == 64, by the dtype the context was finalized with (MP_ERR_SHAPE otherwise, before any launch):
  *     MP_DTYPE_F32_FFT, MP_DTYPE_BF16   any h in [1, 64] (rows past h are zero padding of the 72-point
  *                                       transforms), w == 32 or w == 64
@@ -254,17 +256,33 @@ int mp_circuit_set_nhwc_loop(mp_ctx* ctx, int enable);
 /* the algorithm of the channel-general loop's association-field conv (the compute dtype keeps naming the
  * arithmetic): MP_CN_CONV_DIRECT, the default, is the implicit-GEMM conv; MP_CN_CONV_FFT a forward FFT,
  * an f16x3 spectral product per frequency and an inverse FFT on a 72 x 72 grid (k_circuit_fft.hip,
- * DESIGN.md 3g).  Before mp_finalize_weights, with or without a variant; MP_ERR_STATE on a finalized
- * context, MP_ERR_ARG for another value.  With MP_CN_CONV_FFT set, mp_finalize_weights is
+ * DESIGN.md 3g); MP_CN_CONV_FFT_TILED (since 0.3, additive) the same conv on maps of any size by
+ * overlap-save: the map is cut into windows of at most 64 x 64, each goes through the
+ * 72 x 72 transforms, and the outputs whose whole filter support lay inside the window are kept.  On a
+ * map with h, w <= 64 it is one window and equals MP_CN_CONV_FFT bit for bit.  Before
+ * mp_finalize_weights, with or without a variant; MP_ERR_STATE on a finalized
+ * context, MP_ERR_ARG for another value.  With either FFT conv set, mp_finalize_weights is
  * MP_ERR_UNSUPPORTED, before any launch, for a context that is not on the channel-general loop (k == 64
  * without mp_circuit_set_nhwc_loop: 64 channels have MP_DTYPE_F32_FFT), for k % 4 != 0, and for any
- * dtype but MP_DTYPE_F32_SPLIT; a call with h > 64 or w > 64 is MP_ERR_SHAPE.  Spectra are kept for at
- * most mp_info "nhwc_fft_chunk" images at a time (S + Y within 1 GiB): a larger batch is walked in chunks,
- * which changes no bit of any output.  Range: a conv input (O, I or their gated forms) must keep
- * h * w * max|v| / 64 inside f16 range. */
+ * dtype but MP_DTYPE_F32_SPLIT; under MP_CN_CONV_FFT a call with h > 64 or w > 64 is MP_ERR_SHAPE.
+ * Spectra are kept for at most mp_info "nhwc_fft_chunk" windows (images, up to 64 x 64) at a time (S + Y
+ * within 1 GiB): a larger batch is walked in chunks, which may begin and end inside an image and change
+ * no bit of any output.  Range: a conv input (O, I or their gated forms) must keep
+ * min(h, 64) * min(w, 64) * max|v| / 64 inside f16 range: a window's sum bounds its spectrum, so a
+ * tanh-bounded state uses 64 of the range at any map size. */
 #define MP_CN_CONV_DIRECT 0
 #define MP_CN_CONV_FFT 1
+#define MP_CN_CONV_FFT_TILED 2
 int mp_circuit_set_nhwc_conv(mp_ctx* ctx, int conv);
+
+/* MP_CN_CONV_FFT_TILED's tile plan along one axis of length L (L >= 1) under a filter of size ssf (3, 5 or
+ * 15; R = ssf / 2), on the host (no GPU; the arithmetic the kernels compile, circuit_fft.hpp).  Returns
+ * the tile count and fills, per tile i: origin[i], the map position of the window's local index 0
+ * (the window is [origin, origin + 64), zeros outside the map); out0[i], the local index of its first
+ * output; count[i], the outputs it owns (map positions origin + out0 .. origin + out0 + count - 1).
+ * L <= 64: one tile {0, 0, L}.  L > 64: step T = 64 - 2 R, ceil(L / T) tiles {i T - R, R, min(T, L - i T)}.
+ * MP_ERR_ARG for another ssf, L < 1, a null array, or cap (the arrays' length) below the tile count. */
+int mp_cn_fft_tiles_host(int L, int ssf, int cap, int32_t* origin, int32_t* out0, int32_t* count);
 
 /* ContextualCircuit(X, timesteps, ..., aux).build() for the context's variant.  x, o0, i0, o_out,
  * i_out [n, h, w, 64] NHWC fp32; states_O / states_I [n, timesteps, h, w, 64] or NULL (every step's
@@ -276,7 +294,8 @@ int mp_circuit_set_nhwc_conv(mp_ctx* ctx, int conv);
  * 64; MP_DTYPE_F32: h % 16 == 0, w % 32 == 0; MP_DTYPE_F32_SPLIT: h % 32 == 0, w % 32 == 0), and
  * n * h * w <= 2^24.  On the channel-general loop (k != 64, or mp_circuit_set_nhwc_loop) every 64
  * above is the context's k and any h, w >= 1 is taken; with MP_CN_CONV_FFT (mp_circuit_set_nhwc_conv)
- * h, w in [1, 64], and every conv input keeps h * w * max|v| / 64 inside f16 range. */
+ * h, w in [1, 64], and every conv input keeps h * w * max|v| / 64 inside f16 range; with
+ * MP_CN_CONV_FFT_TILED any h, w >= 1 again, the bound being min(h, 64) * min(w, 64) * max|v| / 64. */
 int mp_hgru_circuit_fwd_var(mp_ctx* ctx, const float* x, const float* o0, const float* i0, int64_t n, int64_t h,
                             int64_t w, int64_t k, int timesteps, int hidden_init, const mp_circuit_variant* variant,
                             float* o_out, float* i_out, float* states_O, float* states_I, void* stream);
@@ -514,8 +533,8 @@ int mp_eval_summary_dev(const void* state, int64_t joints, int64_t T, double* ou
  * "weight_bytes", "fft_loop" (hGRU contexts: 4 = the four-step FFT loop, 6 = the six-launch FFT
  * loop, 0 = a direct-convolution dtype, no FFT path), "channels" (the circuit's channel count k, from
  * p_r at mp_finalize_weights), "nhwc_loop" (1: finalized for the channel-general loop),
- * "nhwc_conv" (1: that loop's conv is the FFT conv, MP_CN_CONV_FFT), "nhwc_fft_chunk" (images per chunk of the
- * FFT conv at the context's k); graph contexts also "graph_kernels" (kernel launches per forward),
+ * "nhwc_conv" (that loop's conv: 1 the FFT conv MP_CN_CONV_FFT, 2 MP_CN_CONV_FFT_TILED, 0 the direct conv),
+ * "nhwc_fft_chunk" (windows -- images, up to 64 x 64 -- per chunk of the FFT conv at the context's k); graph contexts also "graph_kernels" (kernel launches per forward),
  * "graph_streams" (streams the schedule uses), "graph_buffers" (activation buffers after concat placement), "graph_fused_pools" (2x2 max pools
  * computed inside their conv's kernel: MP_GRAPH_FUSE / MP_GRAPH_FUSE_POOL), "graph_fused_1x1" (1x1
  * convs computed by a sibling's kernel) and "graph_path:<conv layer scope>" (the kernel the planned

@@ -61,33 +61,40 @@ def resolve_dtype(name: str, h: int, w: int, k: int = 64, nhwc_loop: bool = Fals
 
 MP_CN_CONV_DIRECT = 0
 MP_CN_CONV_FFT = 1
-NHWC_CONVS = {'direct': MP_CN_CONV_DIRECT, 'fft': MP_CN_CONV_FFT}
+MP_CN_CONV_FFT_TILED = 2
+NHWC_CONVS = {'direct': MP_CN_CONV_DIRECT, 'fft': MP_CN_CONV_FFT, 'fft_tiled': MP_CN_CONV_FFT_TILED}
 NHWC_FFT_MAX_HW = 64
 
 
 def resolve_nhwc_conv(name: str, compute_dtype: str, h: int, w: int, k: int = 64, nhwc_loop: bool = False) -> int:
     """The MP_CN_CONV_* code of the channel-general loop's association-field conv ('direct', the default,
-    or 'fft': mp_circuit_set_nhwc_conv), refusing before a context exists what mp_finalize_weights and
-    the forward call refuse: 'fft' is that loop's (k != 64, or ``nhwc_loop``), needs k % 4 == 0,
-    'fp32_split' arithmetic ('auto' means it there, and never picks 'fft' by itself) and an h x w map of
-    at most 64 x 64."""
+    'fft' or 'fft_tiled': mp_circuit_set_nhwc_conv), refusing before a context exists what
+    mp_finalize_weights and the forward call refuse: the FFT convs are that loop's (k != 64, or
+    ``nhwc_loop``) and need k % 4 == 0 and 'fp32_split' arithmetic ('auto' means it there, and never picks
+    an FFT conv by itself); 'fft' takes an h x w map of at most 64 x 64, 'fft_tiled' (overlap-save over
+    64 x 64 windows) every h, w >= 1.  A conv input must keep min(h, 64) * min(w, 64) * max|v| / 64 inside
+    f16 range."""
     if name not in NHWC_CONVS:
         raise ValueError(f"nhwc_conv must be one of {sorted(NHWC_CONVS)}, got {name!r}")
     if name == 'direct':
         return MP_CN_CONV_DIRECT
     if k == 64 and not nhwc_loop:
-        raise ValueError("nhwc_conv='fft' is the channel-general loop's conv: a 64-channel circuit off that loop "
+        raise ValueError(f"nhwc_conv={name!r} is the channel-general loop's conv: a 64-channel circuit off that loop "
                          "(nhwc_loop=False) has compute_dtype='fp32_fft'")
     if k % 4 != 0:
-        raise ValueError(f"nhwc_conv='fft' transforms 4-channel groups: k = {k} is no multiple of 4 "
+        raise ValueError(f"nhwc_conv={name!r} transforms 4-channel groups: k = {k} is no multiple of 4 "
                          "(nhwc_conv='direct' runs any k)")
     dtype = resolve_dtype(compute_dtype, h, w, k, nhwc_loop)        # 'fp32_fft' / 'bf16' raise here, naming k
     if dtype_code(dtype) != MP_DTYPE_F32_SPLIT:
-        raise ValueError(f"nhwc_conv='fft' of a {k}-channel circuit runs compute_dtype='fp32_split' (an f16x3 "
+        raise ValueError(f"nhwc_conv={name!r} of a {k}-channel circuit runs compute_dtype='fp32_split' (an f16x3 "
                          f"spectral product) only, got {compute_dtype!r}")
+    if name == 'fft_tiled':
+        if h < 1 or w < 1:
+            raise ValueError(f"nhwc_conv='fft_tiled' takes maps of h, w >= 1, got {h} x {w}")
+        return MP_CN_CONV_FFT_TILED
     if not (1 <= h <= NHWC_FFT_MAX_HW and 1 <= w <= NHWC_FFT_MAX_HW):
         raise ValueError(f"nhwc_conv='fft' takes maps up to 64 x 64 (a 72-point transform), got {h} x {w}: "
-                         "nhwc_conv='direct' runs any map size")
+                         "nhwc_conv='fft_tiled' and nhwc_conv='direct' run any map size")
     return MP_CN_CONV_FFT
 
 
@@ -138,6 +145,8 @@ _SIGS = {
     "mp_circuit_var_rule_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                 ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p]),
+    "mp_cn_fft_tiles_host": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p]),
     "mp_dense_fwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                     ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     "mp_hier_fwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
@@ -247,6 +256,16 @@ def circuit_var_rule_host(variant: CircuitVariant, half: int, p, x, o, i, gate, 
     check(load().mp_circuit_var_rule_host(ctypes.byref(variant), int(half), arrs[0].shape[0], *ptr,
                                           ctypes.c_float(rho), out.ctypes.data_as(ctypes.c_void_p)))
     return out
+
+
+def cn_fft_tiles_host(L: int, ssf: int, cap: int = 64):
+    """mp_cn_fft_tiles_host: nhwc_conv='fft_tiled''s plan along an axis of length L as a list of
+    (origin, out0, count) per tile; no GPU."""
+    arrs = [np.zeros(max(int(cap), 1), np.int32) for _ in range(3)]
+    n = load().mp_cn_fft_tiles_host(int(L), int(ssf), int(cap), *[a.ctypes.data_as(ctypes.c_void_p) for a in arrs])
+    if n < 0:
+        check(n)
+    return [tuple(int(a[i]) for a in arrs) for i in range(n)]
 
 
 class MonkeyPoseError(RuntimeError):
@@ -374,7 +393,7 @@ class Context:
         check(self.lib.mp_circuit_set_nhwc_loop(self.h, 1 if enable else 0))
 
     def set_nhwc_conv(self, conv: int) -> None:
-        """the channel-general loop's association-field conv: MP_CN_CONV_DIRECT or MP_CN_CONV_FFT (before
+        """the channel-general loop's association-field conv: MP_CN_CONV_DIRECT, MP_CN_CONV_FFT or MP_CN_CONV_FFT_TILED (before
         ``finalize``)"""
         check(self.lib.mp_circuit_set_nhwc_conv(self.h, int(conv)))
 

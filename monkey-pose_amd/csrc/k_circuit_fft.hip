@@ -1,17 +1,20 @@
-// The channel-general loop's FFT association-field conv (mp_circuit_set_nhwc_conv MP_CN_CONV_FFT): the
-// SAME conv P = p_r * A of NHWC fp32 maps [n, h, w, k], k % 4 == 0, h, w <= 64, as three launches
-//   cn_fft_fwd    A [n,h,w,k]  -> S   72 x 72 real-input FFT per (image, 4-channel group), f16 hi / lo split
+// The channel-general loop's FFT association-field conv (mp_circuit_set_nhwc_conv MP_CN_CONV_FFT and
+// MP_CN_CONV_FFT_TILED): the SAME conv P = p_r * A of NHWC fp32 maps [n, h, w, k], k % 4 == 0, as three
+// launches over the map's tiles (circuit_fft.hpp: the tile plan; one tile when h, w <= 64, which is all
+// MP_CN_CONV_FFT takes, else overlap-save windows of 64 x 64)
+//   cn_fft_fwd    A [n,h,w,k]  -> S   72 x 72 real-input FFT per (tile, 4-channel group), f16 hi / lo split
 //   cn_spec_gemm  S, Gc        -> Y   per frequency Y[b][co] = sum_ci S[b][ci] G[ci][co], f16x3 on the matrix cores
-//   cn_fft_inv    Y            -> P   inverse FFT, the live h x w pixels stored
+//   cn_fft_inv    Y            -> P   inverse FFT, the pixels the tile owns stored at their map position
 // on the 72-point transforms of fft_dev.hpp.  Layouts and the padding rules: circuit_fft.hpp.  The
 // 64-channel loops keep their own kernels (k_fft.hip, k_fft4.hip); nothing here is shared with them
 // but fft_dev.hpp.
 //
-// Every kernel computes an image from that image alone and in an order that depends on k alone, so an
-// output does not depend on the batch, on the image's place in it or on the conv chunk it falls in.
+// Every kernel computes a tile from that tile alone and in an order that depends on k alone, so an
+// output does not depend on the batch, on the image's place in it or on the conv chunk its tiles fall in.
 //
-// Range: S holds SPEC_SCALE * (the transform of the map), bounded by SPEC_SCALE * sum|v| over the map, in
-// f16: a conv input must keep h * w * max|v| / 64 inside f16 range (65504), as on the 64-channel FFT path.
+// Range: S holds SPEC_SCALE * (the transform of a window), bounded by SPEC_SCALE * sum|v| over the window,
+// in f16: a conv input must keep min(h, 64) * min(w, 64) * max|v| / 64 inside f16 range (65504), as on the
+// 64-channel FFT path.
 #include "circuit_fft.hpp"
 #include "fft_dev.hpp"
 #include "mp_kernels.hpp"
@@ -27,9 +30,9 @@ constexpr int CF_LDS = FX * 4 * CF_TLD;     // complex elements of a transform b
 static_assert(128 * CF_RLD <= CF_LDS && 64 * 4 * FX <= CF_LDS, "LDS plan of the inverse");
 constexpr int CF_FS = FX * 4;               // stride of one fy step in 8-byte units (f = fy * 37 + fx)
 
-// Block -> (image, channel group), XCD-aware.  The k / 4 groups of a pixel are 16 bytes each, so eight
+// Block -> (tile, channel group), XCD-aware.  The k / 4 groups of a pixel are 16 bytes each, so eight
 // neighbouring groups share every 128-byte line of the map; workgroups are dispatched round-robin over
-// the 8 XCDs (blocks i and i + 8 share one), so the eight groups of a (image, line) unit are placed 8
+// the 8 XCDs (blocks i and i + 8 share one), so the eight groups of a (tile, line) unit are placed 8
 // blocks apart: one L2 moves each line once.  64 blocks = 8 units x 8 groups.
 __device__ __forceinline__ bool cf_block(int blk, int n, int nq, int& b, int& cq) {
   const int nl = (nq + 7) >> 3;
@@ -40,29 +43,63 @@ __device__ __forceinline__ bool cf_block(int blk, int n, int nq, int& b, int& cq
 }
 int cf_grid(int n, int k) { return (n * ((cnf_nq(k) + 7) / 8) + 7) / 8 * 64; }
 
-// forward: one block per (image, 4-channel group).  Row phase (128 threads): row y, channel pair p, the
-// two real rows packed as one complex transform; LDS transpose; column phase (148 threads): column
-// (fx, c) of the 37-column half spectrum.  Rows >= H and columns >= W are zeros of the transform: such
-// rows are neither loaded nor transformed, such columns are loaded from a clamped (live) address and
-// zeroed.
+// The tiles of a launch: tile t of the launch is tile t0 + t of the maps' n * ty * tx, image-major then
+// tile row then tile column, and S / Y hold it at index t (a conv chunk may begin and end inside an image).
+struct CfTile {
+  int b;        // image
+  int oy, ox;   // map position of the window's local (0, 0); negative in a leading halo
+  int ly, lx;   // local index of the first output the tile owns
+  int py, px;   // its map position
+  int cy, cx;   // outputs the tile owns
+};
+// TILED false: every image is one tile (g.ty == g.tx == 1, h, w <= 64), the plan's constants folded
+template <bool TILED>
+__device__ __forceinline__ CfTile cf_tile(const CnfMap& g, int t) {
+  if constexpr (!TILED) return CfTile{g.t0 + t, 0, 0, 0, 0, 0, 0, g.H, g.W};
+  const int gt = g.t0 + t, tpi = g.ty * g.tx;
+  CfTile r;
+  r.b = gt / tpi;
+  const int rem = gt - r.b * tpi, iy = rem / g.tx, ix = rem - iy * g.tx;
+  r.oy = cnf_tile_origin(g.H, g.ssf, iy);
+  r.ox = cnf_tile_origin(g.W, g.ssf, ix);
+  r.ly = cnf_tile_out0(g.H, g.ssf);
+  r.lx = cnf_tile_out0(g.W, g.ssf);
+  r.py = cnf_tile_pos(g.H, g.ssf, iy);
+  r.px = cnf_tile_pos(g.W, g.ssf, ix);
+  r.cy = cnf_tile_count(g.H, g.ssf, iy);
+  r.cx = cnf_tile_count(g.W, g.ssf, ix);
+  return r;
+}
+
+// forward: one block per (tile, 4-channel group).  Row phase (128 threads): window row y, channel pair
+// p, the two real rows packed as one complex transform; LDS transpose; column phase (148 threads):
+// column (fx, c) of the 37-column half spectrum.  Window rows and columns outside the map are zeros of the
+// transform: such rows, leading or trailing, are neither loaded nor transformed (the column phase
+// reads them as zeros, never from LDS), such columns are loaded from a clamped (live) address and
+// zeroed.  The two instantiations run the same arithmetic in the same order: a map of one tile gives the
+// same bytes through either (the launchers send it through TILED false, MP_CN_CONV_FFT's kernel).
+template <bool TILED>
 __global__ __launch_bounds__(FNT, 2) void cn_fft_fwd_kernel(const float* __restrict__ src, void* __restrict__ S, int n,
-                                                            int H, int W, int k) {
+                                                            CnfMap g, int k) {
   __shared__ cpx T[CF_LDS];
   int b, cq;
   if (!cf_block(blockIdx.x, n, k >> 2, b, cq)) return;
+  const CfTile tl = cf_tile<TILED>(g, b);
+  const int H = g.H, W = g.W;
   const int tid = threadIdx.x;
   if (tid < 128) {
     const int y = tid >> 1, p = tid & 1;
-    if (y < H) {   // a lane pair shares y: both lanes of every DPP exchange below are active
+    const int my = tl.oy + y;
+    if (my >= 0 && my < H) {   // a lane pair shares y: both lanes of every DPP exchange below are active
       cpx v[72];
       // lane p of the row's pair loads all 4 channels of pixel 2 j + p (one 16-byte load at stride 4 k
       // bytes), then the pair swaps the channel pair the other lane transforms (quad_perm [1,0,3,2])
-      const float* row = src + ((size_t)b * H + y) * W * k + 4 * cq;
+      const float* row = src + ((size_t)tl.b * H + my) * W * k + 4 * cq;
 #pragma unroll
       for (int j = 0; j < 32; ++j) {
-        const int x = 2 * j + p;
-        f32x4 u = *reinterpret_cast<const f32x4*>(row + (size_t)min(x, W - 1) * k);
-        if (x >= W) u = f32x4{0.f, 0.f, 0.f, 0.f};
+        const int x = tl.ox + 2 * j + p;
+        f32x4 u = *reinterpret_cast<const f32x4*>(row + (size_t)min(max(x, 0), W - 1) * k);
+        if (x < 0 || x >= W) u = f32x4{0.f, 0.f, 0.f, 0.f};
         const cpx lo = {u[0], u[1]}, hi = {u[2], u[3]};
         const cpx mine = p ? hi : lo, send = p ? lo : hi;
         const cpx recv = {__int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(send.x), 0xB1, 0xF, 0xF, false)),
@@ -89,7 +126,8 @@ __global__ __launch_bounds__(FNT, 2) void cn_fft_fwd_kernel(const float* __restr
   const int fx = tid >> 2, c = tid & 3;
   cpx v[72];
 #pragma unroll
-  for (int y = 0; y < 72; ++y) v[y] = (y < 64 && y < H) ? T[tid * CF_TLD + y] : cpx{0.f, 0.f};   // rows >= H: never written
+  for (int y = 0; y < 72; ++y)   // rows outside the map: never written
+    v[y] = (y < 64 && tl.oy + y >= 0 && tl.oy + y < H) ? T[tid * CF_TLD + y] : cpx{0.f, 0.f};
   fft72<-1>(v);
   // the 32-byte entry of (f, cq): [hi c0 | hi c1 | hi c2 | hi c3 | lo c0 | lo c1 | lo c2 | lo c3], 4 B
   // each = f16 (re, im); lane c of the quad stores bytes 8 c .. 8 c + 7 (two quad_perms regroup the
@@ -113,12 +151,15 @@ __global__ __launch_bounds__(FNT, 2) void cn_fft_fwd_kernel(const float* __restr
 }
 
 // inverse: Y -> P, the forward kernel run backwards (columns, LDS transpose, Hermitian-extended row
-// pairs), the rows parked in LDS and the live pixels stored pixel-major, 16 bytes each, times unscale
+// pairs; only the window rows that hold outputs), the rows parked in LDS and the cy x cx pixels the tile
+// owns stored pixel-major at their map position, 16 bytes each, times unscale
+template <bool TILED>
 __global__ __launch_bounds__(FNT, 2) void cn_fft_inv_kernel(const void* __restrict__ Y, float* __restrict__ P, int n,
-                                                            int H, int W, int k, float unscale) {
+                                                            CnfMap g, int k, float unscale) {
   __shared__ cpx T[CF_LDS];
   int b, cq;
   if (!cf_block(blockIdx.x, n, k >> 2, b, cq)) return;
+  const CfTile tl = cf_tile<TILED>(g, b);
   const int tid = threadIdx.x;
   if (tid < FX * 4) {
     const int fx = tid >> 2, c = tid & 3;
@@ -132,7 +173,7 @@ __global__ __launch_bounds__(FNT, 2) void cn_fft_inv_kernel(const void* __restri
   }
   lds_barrier();
   const int y = tid >> 1, p = tid & 1;
-  const bool live = tid < 128 && y < H;
+  const bool live = tid < 128 && y >= tl.ly && y < tl.ly + tl.cy;
   {
     cpx v[72];
     if (live) {
@@ -153,11 +194,12 @@ __global__ __launch_bounds__(FNT, 2) void cn_fft_inv_kernel(const void* __restri
     }
   }
   lds_barrier();
-  float* dst = P + (size_t)b * H * W * k + 4 * cq;
-  for (int i = tid; i < H * W; i += FNT) {
-    const int yy = i / W, x = i - yy * W;
-    const cpx a = T[(2 * yy) * CF_RLD + x], c = T[(2 * yy + 1) * CF_RLD + x];
-    *reinterpret_cast<f32x4*>(dst + (size_t)i * k) = f32x4{a.x, a.y, c.x, c.y} * unscale;
+  float* dst = P + (((size_t)tl.b * g.H + tl.py) * g.W + tl.px) * k + 4 * cq;
+  for (int i = tid; i < tl.cy * tl.cx; i += FNT) {
+    const int yy = i / tl.cx, x = i - yy * tl.cx;
+    const int r = 2 * (tl.ly + yy) * CF_RLD + tl.lx + x;
+    const cpx a = T[r], c = T[r + CF_RLD];
+    *reinterpret_cast<f32x4*>(dst + ((size_t)yy * g.W + x) * k) = f32x4{a.x, a.y, c.x, c.y} * unscale;
   }
 }
 
@@ -371,8 +413,11 @@ hipError_t build_cn_spec_weights(const float* w, int ks, int k, void* Gc, float*
   return e;
 }
 
-hipError_t launch_cn_fft_fwd(const float* act, void* S, int n, int H, int W, int k, hipStream_t st) {
-  hipLaunchKernelGGL(cn_fft_fwd_kernel, dim3(cf_grid(n, k)), dim3(FNT), 0, st, act, S, n, H, W, k);
+hipError_t launch_cn_fft_fwd(const float* act, void* S, int n, const CnfMap& g, int k, hipStream_t st) {
+  if (g.ty * g.tx == 1)
+    hipLaunchKernelGGL(cn_fft_fwd_kernel<false>, dim3(cf_grid(n, k)), dim3(FNT), 0, st, act, S, n, g, k);
+  else
+    hipLaunchKernelGGL(cn_fft_fwd_kernel<true>, dim3(cf_grid(n, k)), dim3(FNT), 0, st, act, S, n, g, k);
   return hipGetLastError();
 }
 
@@ -383,8 +428,11 @@ hipError_t launch_cn_spec_gemm(const void* S, const void* Gc, void* Y, int n, in
   return hipGetLastError();
 }
 
-hipError_t launch_cn_fft_inv(const void* Y, float* P, int n, int H, int W, int k, float unscale, hipStream_t st) {
-  hipLaunchKernelGGL(cn_fft_inv_kernel, dim3(cf_grid(n, k)), dim3(FNT), 0, st, Y, P, n, H, W, k, unscale);
+hipError_t launch_cn_fft_inv(const void* Y, float* P, int n, const CnfMap& g, int k, float unscale, hipStream_t st) {
+  if (g.ty * g.tx == 1)
+    hipLaunchKernelGGL(cn_fft_inv_kernel<false>, dim3(cf_grid(n, k)), dim3(FNT), 0, st, Y, P, n, g, k, unscale);
+  else
+    hipLaunchKernelGGL(cn_fft_inv_kernel<true>, dim3(cf_grid(n, k)), dim3(FNT), 0, st, Y, P, n, g, k, unscale);
   return hipGetLastError();
 }
 

@@ -145,6 +145,8 @@ mp_circuit_variant pose_variant() {
 
 mpcv::CircuitVariant pod_variant(const mp_circuit_variant& m);
 
+const char* cn_conv_name(int mode) { return mode == MP_CN_CONV_FFT_TILED ? "MP_CN_CONV_FFT_TILED" : "MP_CN_CONV_FFT"; }
+
 // the channel-general loop's weights (k from p_r): p_r, i_r and o_r as [K][k] implicit-GEMM matrices of
 // the graph runtime's launchers (f16x3 under MP_DTYPE_F32_SPLIT, exact fp32 under MP_DTYPE_F32), the
 // [CV_VECS][k] table, and k zeros for the association-field conv's bias
@@ -155,12 +157,14 @@ void finalize_circuit_nhwc(mp_ctx* c, const RawWeight& p_r) {
          "a " + std::to_string(k) + "-channel circuit" + (k == 64 ? " on the channel-general loop" : "") +
              " runs MP_DTYPE_F32_SPLIT or MP_DTYPE_F32: the FFT path's spectral GEMM and map layouts "
              "(MP_DTYPE_F32_FFT, MP_DTYPE_BF16) are 64 channels wide");
-  const bool fft = c->cn_conv_mode == MP_CN_CONV_FFT;
+  // MP_CN_CONV_FFT and MP_CN_CONV_FFT_TILED: the same kernels and spectral weights, one map-size check apart (cn_check)
+  const bool fft = c->cn_conv_mode != MP_CN_CONV_DIRECT;
+  const std::string mode = cn_conv_name(c->cn_conv_mode);
   if (fft && k % 4 != 0)
-    fail(MP_ERR_UNSUPPORTED, "MP_CN_CONV_FFT transforms 4-channel groups: k = " + std::to_string(k) +
+    fail(MP_ERR_UNSUPPORTED, mode + " transforms 4-channel groups: k = " + std::to_string(k) +
                                  " is no multiple of 4 (MP_CN_CONV_DIRECT runs any k)");
   if (fft && c->dtype != MP_DTYPE_F32_SPLIT)
-    fail(MP_ERR_UNSUPPORTED, "MP_CN_CONV_FFT of a " + std::to_string(k) +
+    fail(MP_ERR_UNSUPPORTED, mode + " of a " + std::to_string(k) +
                                  "-channel circuit runs MP_DTYPE_F32_SPLIT (an f16x3 spectral product) only");
   const auto& i_r = c->need("contextual_circuit/i_r", {1, 1, k, k});
   const auto& o_r = c->need("contextual_circuit/o_r", {1, 1, k, k});
@@ -184,6 +188,7 @@ void finalize_circuit_nhwc(mp_ctx* c, const RawWeight& p_r) {
   c->cn_cv = pod_variant(m);
   finalize_variant_vecs(c, m, k);
   c->cn_fft = fft;
+  c->cn_fft_tiled = c->cn_conv_mode == MP_CN_CONV_FFT_TILED;
 }
 
 void finalize_circuit(mp_ctx* c, const std::vector<float>* outs, const std::vector<float>* outt) {
@@ -202,10 +207,10 @@ void finalize_circuit(mp_ctx* c, const std::vector<float>* outs, const std::vect
   c->ssf = (int)ps[0];
   c->chan = (int)ps[2];
   c->nhwc = any_k && (c->chan != 64 || c->nhwc_flag);
-  c->cn_fft = false;
-  if (c->cn_conv_mode == MP_CN_CONV_FFT && !c->nhwc)
+  c->cn_fft = c->cn_fft_tiled = false;
+  if (c->cn_conv_mode != MP_CN_CONV_DIRECT && !c->nhwc)
     fail(MP_ERR_UNSUPPORTED,
-         "MP_CN_CONV_FFT is the channel-general loop's: a " + std::to_string(c->chan) +
+         std::string(cn_conv_name(c->cn_conv_mode)) + " is the channel-general loop's: a " + std::to_string(c->chan) +
              "-channel circuit off that loop (no mp_circuit_set_nhwc_loop) has MP_DTYPE_F32_FFT");
   if (c->nhwc) {
     finalize_circuit_nhwc(c, it->second);
@@ -936,20 +941,23 @@ void cn_conv(mp_ctx* c, const mp_ctx::PackedLayer& L, const float* src, const fl
   hip_check(L.x3 ? launch_igemm_x3(a, L.w.p, L.wus, st) : launch_igemm_conv(a, st), what);
 }
 
-// dst = p_r * src (SAME, no bias) as forward FFT, spectral product, inverse FFT (k_circuit_fft.hip), the
-// batch walked in chunks of cnf_chunk(k) images so that S + Y stay within CNF_WS_BYTES; every kernel
-// computes an image from that image alone, so the chunking changes no bit of any output
+// dst = p_r * src (SAME, no bias) as forward FFT, spectral product, inverse FFT (k_circuit_fft.hip) over
+// the batch's n * ty * tx tiles (circuit_fft.hpp: one tile per image up to 64 x 64, all MP_CN_CONV_FFT
+// takes), walked in chunks of cnf_chunk(k) tiles so that S + Y stay within CNF_WS_BYTES.  A chunk may begin
+// and end inside an image; every kernel computes a tile from that tile alone, so the chunking changes no
+// bit of any output
 void cn_conv_fft(mp_ctx* c, const float* src, float* dst, int n, int H, int W, hipStream_t st, const char* what) {
   const int k = c->chan, chunk = cnf_chunk(k);
-  const size_t spec = cnf_image_bytes(k) * (size_t)std::min(n, chunk);
+  CnfMap g{H, W, c->ssf, cnf_tiles(H, c->ssf), cnf_tiles(W, c->ssf), 0};
+  const int nt = n * g.ty * g.tx;   // <= n h w <= 2^24 (cn_check)
+  const size_t spec = cnf_image_bytes(k) * (size_t)std::min(nt, chunk);
   c->specS.alloc(spec);
   c->specY.alloc(spec);
-  for (int b0 = 0; b0 < n; b0 += chunk) {
-    const int nb = std::min(chunk, n - b0);
-    const size_t off = (size_t)b0 * H * W * k;
+  for (g.t0 = 0; g.t0 < nt; g.t0 += chunk) {
+    const int nb = std::min(chunk, nt - g.t0);
     {
       ProfScope ps(c, st, "cn_fft_fwd");
-      hip_check(launch_cn_fft_fwd(src + off, c->specS.p, nb, H, W, k, st), what);
+      hip_check(launch_cn_fft_fwd(src, c->specS.p, nb, g, k, st), what);
     }
     {
       ProfScope ps(c, st, "cn_spec_gemm");
@@ -957,7 +965,7 @@ void cn_conv_fft(mp_ctx* c, const float* src, float* dst, int n, int H, int W, h
     }
     {
       ProfScope ps(c, st, "cn_fft_inv");
-      hip_check(launch_cn_fft_inv(c->specY.p, dst + off, nb, H, W, k, c->cn_fft_us, st), what);
+      hip_check(launch_cn_fft_inv(c->specY.p, dst, nb, g, k, c->cn_fft_us, st), what);
     }
   }
 }
@@ -1046,9 +1054,9 @@ void cn_check(mp_ctx* c, int64_t n, int64_t h, int64_t w, int64_t k, int timeste
   if (k != c->chan)
     fail(MP_ERR_SHAPE, "channel count k must be " + std::to_string(c->chan) + ", the context's (from p_r)");
   if (n <= 0 || h <= 0 || w <= 0 || n * h * w > (int64_t)1 << 24) fail(MP_ERR_SHAPE, "empty or oversized input");
-  if (c->cn_fft && (h > CNF_MAX_HW || w > CNF_MAX_HW))
+  if (c->cn_fft && !c->cn_fft_tiled && (h > CNF_MAX_HW || w > CNF_MAX_HW))
     fail(MP_ERR_SHAPE, "MP_CN_CONV_FFT takes maps up to 64 x 64 (a 72-point transform), got " + std::to_string(h) +
-                           " x " + std::to_string(w) + ": MP_CN_CONV_DIRECT runs any map size");
+                           " x " + std::to_string(w) + ": MP_CN_CONV_FFT_TILED and MP_CN_CONV_DIRECT run any map size");
   if (timesteps < 1 || (c->cn_cv.adapt && timesteps > (int)c->rho.size()))
     fail(MP_ERR_ARG, "timesteps must be at least 1 and, with adaptation, at most len(rho)");
 }
@@ -1561,8 +1569,8 @@ int mp_circuit_set_nhwc_conv(mp_ctx* ctx, int conv) {
     if (ctx->model != MP_MODEL_HGRU_CIRCUIT)
       fail(MP_ERR_STATE, "the channel-general loop runs on an MP_MODEL_HGRU_CIRCUIT context");
     if (ctx->finalized) fail(MP_ERR_STATE, "mp_circuit_set_nhwc_conv after mp_finalize_weights: set it before finalizing");
-    if (conv != MP_CN_CONV_DIRECT && conv != MP_CN_CONV_FFT)
-      fail(MP_ERR_ARG, "conv must be MP_CN_CONV_DIRECT or MP_CN_CONV_FFT, got " + std::to_string(conv));
+    if (conv != MP_CN_CONV_DIRECT && conv != MP_CN_CONV_FFT && conv != MP_CN_CONV_FFT_TILED)
+      fail(MP_ERR_ARG, "conv must be MP_CN_CONV_DIRECT, MP_CN_CONV_FFT or MP_CN_CONV_FFT_TILED, got " + std::to_string(conv));
     ctx->cn_conv_mode = conv;
   });
 }
@@ -1646,6 +1654,22 @@ int mp_circuit_var_rule_host(const mp_circuit_variant* variant, int half, int64_
   });
 }
 
+int mp_cn_fft_tiles_host(int L, int ssf, int cap, int32_t* origin, int32_t* out0, int32_t* count) {
+  int tiles = 0;
+  const int rc = guard([&] {
+    if (!(ssf == 3 || ssf == 5 || ssf == 15) || L < 1 || !origin || !out0 || !count)
+      fail(MP_ERR_ARG, "mp_cn_fft_tiles_host: ssf must be 3, 5 or 15, L at least 1, the arrays non-null");
+    tiles = cnf_tiles(L, ssf);
+    if (cap < tiles) fail(MP_ERR_ARG, "mp_cn_fft_tiles_host: the axis has " + std::to_string(tiles) + " tiles, cap is smaller");
+    for (int i = 0; i < tiles; ++i) {
+      origin[i] = cnf_tile_origin(L, ssf, i);
+      out0[i] = cnf_tile_out0(L, ssf);
+      count[i] = cnf_tile_count(L, ssf, i);
+    }
+  });
+  return rc == MP_OK ? tiles : rc;
+}
+
 int mp_info(mp_ctx* ctx, const char* key, int64_t* value) {
   return guard([&] {
     if (!ctx || !key || !value) fail(MP_ERR_ARG, "mp_info: null pointer");
@@ -1661,9 +1685,9 @@ int mp_info(mp_ctx* ctx, const char* key, int64_t* value) {
       *value = ctx->chan;
     else if (k == "nhwc_loop")   // 1: finalized for the channel-general loop
       *value = ctx->nhwc ? 1 : 0;
-    else if (k == "nhwc_conv")   // 1: finalized with the FFT association-field conv (MP_CN_CONV_FFT)
-      *value = ctx->cn_fft ? 1 : 0;
-    else if (k == "nhwc_fft_chunk")   // images per chunk of that conv at this context's channel count
+    else if (k == "nhwc_conv")   // finalized with the FFT association-field conv: 1 MP_CN_CONV_FFT, 2 MP_CN_CONV_FFT_TILED
+      *value = ctx->cn_fft ? (ctx->cn_fft_tiled ? MP_CN_CONV_FFT_TILED : MP_CN_CONV_FFT) : 0;
+    else if (k == "nhwc_fft_chunk")   // tiles (images, on maps up to 64 x 64) per chunk of that conv at this context's channel count
       *value = cnf_chunk(ctx->chan);
     else if (k == "finalized")
       *value = ctx->finalized ? 1 : 0;

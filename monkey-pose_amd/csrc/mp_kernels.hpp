@@ -2,6 +2,7 @@
 #pragma once
 #include "mp_common.hpp"
 #include "circuit_var.hpp"
+#include "circuit_fft.hpp"
 #include "../../include/monkeypose.h"
 
 namespace mp {
@@ -144,13 +145,15 @@ hipError_t launch_circuit_nhwc_in(const CnArgs& a, hipStream_t st);
 hipError_t launch_circuit_nhwc_out(const CnArgs& a, hipStream_t st);
 // dst = src * sigmoid(gp) over total elements: the gated conv inputs A_in = O g1, B_in = I' g2
 hipError_t launch_circuit_nhwc_gate(const float* src, const float* gp, float* dst, int64_t total, hipStream_t st);
-// k_circuit_fft.hip: the channel-general loop's FFT association-field conv (MP_CN_CONV_FFT; k % 4 == 0,
-// maps up to 64 x 64; sizes and layouts in circuit_fft.hpp).  w: p_r [ks][ks][k][k] on the device;
-// Gc: cnf_weight_bytes(k); S, Y: cnf_image_bytes(k) per image; unscale multiplies the inverse's output
+// k_circuit_fft.hip: the channel-general loop's FFT association-field conv (MP_CN_CONV_FFT, maps up to
+// 64 x 64, and MP_CN_CONV_FFT_TILED, any map; k % 4 == 0; sizes, layouts and the tile plan in
+// circuit_fft.hpp).  w: p_r [ks][ks][k][k] on the device; Gc: cnf_weight_bytes(k); n: the launch's tiles
+// (g.t0 .. g.t0 + n - 1 of the maps act / P point to); S, Y: cnf_image_bytes(k) per tile; unscale
+// multiplies the inverse's output
 hipError_t build_cn_spec_weights(const float* w, int ks, int k, void* Gc, float* unscale);
-hipError_t launch_cn_fft_fwd(const float* act, void* S, int n, int H, int W, int k, hipStream_t st);
+hipError_t launch_cn_fft_fwd(const float* act, void* S, int n, const CnfMap& g, int k, hipStream_t st);
 hipError_t launch_cn_spec_gemm(const void* S, const void* Gc, void* Y, int n, int k, hipStream_t st);
-hipError_t launch_cn_fft_inv(const void* Y, float* P, int n, int H, int W, int k, float unscale, hipStream_t st);
+hipError_t launch_cn_fft_inv(const void* Y, float* P, int n, const CnfMap& g, int k, float unscale, hipStream_t st);
 // k_igemm.hip (dense / hierarchical regressors)
 struct IgemmArgs {
   const float* x;      // input view: pixel (n,y,x) channel ci at x[((n*H+y)*W+x)*ldx + cix + ci]

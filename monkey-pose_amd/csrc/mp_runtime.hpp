@@ -168,7 +168,8 @@ struct mp_ctx {
   PackedLayer cn_p, cn_ir, cn_or;       // p_r, i_r, o_r as [K][k] implicit-GEMM weights
   DevBuf cn_zero;                       // k zeros: the bias of the association-field conv
   int cn_conv_mode = MP_CN_CONV_DIRECT; // mp_circuit_set_nhwc_conv: the association-field conv's algorithm
-  bool cn_fft = false;                  // finalized with MP_CN_CONV_FFT (k_circuit_fft.hip; S / Y in specS / specY)
+  bool cn_fft = false;                  // finalized with MP_CN_CONV_FFT or _FFT_TILED (k_circuit_fft.hip; S / Y in specS / specY)
+  bool cn_fft_tiled = false;            // ... with MP_CN_CONV_FFT_TILED: maps of any size, cut into 64 x 64 windows
   DevBuf cn_fft_g;                      // its compact split spectral weights of p_r
   float cn_fft_us = 1.f;                // 1 / (their scale * SPEC_SCALE)
 

@@ -218,7 +218,11 @@ class ContextualCircuit(object):
         ``nhwc_conv='fft'`` runs that loop's association-field conv as an FFT conv (k % 4 == 0,
         'fp32_split', maps up to 64 x 64, conv inputs with h * w * max|v| / 64 inside f16 range; see
         _lib.resolve_nhwc_conv); 'direct', the default, is the implicit-GEMM conv.  'auto' never picks 'fft':
-        at ssf 3 and 5 the direct conv is the faster one (README)."""
+        at ssf 3 and 5 the direct conv is the faster one (README).
+        ``nhwc_conv='fft_tiled'`` is that FFT conv on maps of any size (overlap-save over
+        windows of at most 64 x 64, the other conditions of 'fft'; one window, and 'fft' bit for bit, up to
+        64 x 64).  Its range bound is per window: conv inputs keep min(h, 64) * min(w, 64) * max|v| / 64
+        inside f16 range, so tanh-bounded states use 64 of it at any map size.  'auto' never picks it."""
         import torch
         X = self.X
         if not isinstance(X, torch.Tensor) or not X.is_cuda:

@@ -1,4 +1,4 @@
-"""Times the channel-general circuit loop at n = 64, 64 x 64, ssf = 15, T = 8, fp32_split, in one
+"""Times the channel-general circuit loop at n = 64, 64 x 64 (--hw H or HxW), ssf = 15, T = 8, fp32_split, in one
 process, for the hgru_pose aux and the module's default aux (both through mp_hgru_circuit_fwd_var):
 
   k32, k128     32 and 128 channels on the channel-general loop
@@ -6,6 +6,9 @@ process, for the hgru_pose aux and the module's default aux (both through mp_hgr
   k64_general   64 channels on the general loop (k_conv64x3.hip + k_circuit_var.hip): the reference time
   k32_fft, k64_nhwc_fft, k128_fft   the same contexts with the FFT association-field conv
                 (mp_circuit_set_nhwc_conv MP_CN_CONV_FFT, k_circuit_fft.hip)
+  k32_fft_tiled, k64_nhwc_fft_tiled, k128_fft_tiled   the tiled FFT conv (MP_CN_CONV_FFT_TILED):
+                maps of any size; on a map above 64 x 64 the forms that refuse it ('fft', the general
+                loop's fp32_fft) are left out
   k64_general_fft   64 channels on the general loop's fp32_fft (k_fft.hip)
 
 Device events around one forward, warm-up, then the median of --runs forwards per form, the forms
@@ -35,27 +38,36 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 AUX = {"pose": {'gru_gates': True, 'adapation': True}, "defaults": {}}
-# name, k, on the channel-general loop, its conv ('direct' / 'fft'), compute dtype
+# name, k, on the channel-general loop, its conv ('direct' / 'fft' / 'fft_tiled'), compute dtype
 FORMS = (("k32", 32, True, "direct", "fp32_split"), ("k32_fft", 32, True, "fft", "fp32_split"),
+         ("k32_fft_tiled", 32, True, "fft_tiled", "fp32_split"),
          ("k128", 128, True, "direct", "fp32_split"), ("k128_fft", 128, True, "fft", "fp32_split"),
+         ("k128_fft_tiled", 128, True, "fft_tiled", "fp32_split"),
          ("k64_nhwc", 64, True, "direct", "fp32_split"), ("k64_nhwc_fft", 64, True, "fft", "fp32_split"),
+         ("k64_nhwc_fft_tiled", 64, True, "fft_tiled", "fp32_split"),
          ("k64_general", 64, False, "direct", "fp32_split"), ("k64_general_fft", 64, False, "direct", "fp32_fft"))
 PROFILE_KEYS = ("cn_in", "cn_out", "cn_gate", "cn_conv", "cn_gate_conv", "cn_fft_fwd", "cn_spec_gemm", "cn_fft_inv")
 CONV_KEYS = ("cn_conv", "cn_gate_conv", "cn_fft_fwd", "cn_spec_gemm", "cn_fft_inv")
 NF = 72 * 37
 
 
-def fft_conv_bytes(n, h, w, k, T):
+def tiles(L, ssf):
+    """circuit_fft.hpp cnf_tiles: windows along an axis of length L"""
+    return 1 if L <= 64 else -(-L // (64 - 2 * (ssf // 2)))
+
+
+def fft_conv_bytes(n, h, w, k, T, ssf):
     """algorithmic bytes of the 2 T launches of each FFT-conv kernel in one forward (circuit_fft.hpp): the
-    map and one spectrum for a transform; S, Y and the compact weights for the product"""
+    map and one spectrum per window for a transform; S, Y and the compact weights for the product"""
     m = n * h * w * k * 4
-    spec = n * (k // 4) * NF * 32
+    spec = n * tiles(h, ssf) * tiles(w, ssf) * (k // 4) * NF * 32
     wts = NF * 2 * ((k // 4 + 1) // 2 * 2) * ((k + 31) // 32 * 32) * 16
     return {"cn_fft_fwd": 2 * T * (m + spec), "cn_fft_inv": 2 * T * (m + spec), "cn_spec_gemm": 2 * T * (2 * spec + wts)}
 
 
 def fft_conv_flops(n, k, T):
-    """real flops of the spectral product's 2 T launches as issued: 3 products (f16x3) of 2k x 2k x n per frequency"""
+    """real flops of the spectral product's 2 T launches as issued: 3 products (f16x3) of 2k x 2k x n per
+    frequency, n the batch's windows"""
     return 2 * T * 3 * 2 * (2 * k) * (2 * k) * n * NF
 
 
@@ -75,7 +87,7 @@ def main():
     ap.add_argument("--runs", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=64)
-    ap.add_argument("--hw", type=int, default=64)
+    ap.add_argument("--hw", default="64", help="map size: H (square) or HxW")
     ap.add_argument("--ssf", type=int, default=15)
     ap.add_argument("--timesteps", type=int, default=8)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "channels", "time_channels.json"))
@@ -86,15 +98,19 @@ def main():
     import bench
     mp = importlib.import_module("monkey-pose_amd")
     L, W, M = mp._lib, mp.weights, mp.hgru_module
-    n, hw, T = a.batch, a.hw, a.timesteps
+    n, T = a.batch, a.timesteps
+    h, w = (int(v) for v in (a.hw.split("x") if "x" in a.hw else (a.hw, a.hw)))
+    ntile = tiles(h, a.ssf) * tiles(w, a.ssf)
     dev = torch.device("cuda", 0)
     st = L.current_stream(dev)
     bufs = {}
     chosen = [f for f in FORMS if not a.forms or f[0] in a.forms.split(",")]
+    if max(h, w) > 64:      # 'fft' and the general loop's fp32_fft take maps up to 64 x 64
+        chosen = [f for f in chosen if f[3] != "fft" and f[4] != "fp32_fft"]
     for k in sorted({f[1] for f in chosen}):
-        x = torch.from_numpy(W.synth_hidden((n, hw, hw, k), seed=3, name="X", limit=1.0)).to(dev)
-        o0 = torch.from_numpy(W.synth_hidden((n, hw, hw, k), seed=7)).to(dev)
-        i0 = torch.from_numpy(W.synth_hidden((n, hw, hw, k), seed=1007)).to(dev)
+        x = torch.from_numpy(W.synth_hidden((n, h, w, k), seed=3, name="X", limit=1.0)).to(dev)
+        o0 = torch.from_numpy(W.synth_hidden((n, h, w, k), seed=7)).to(dev)
+        i0 = torch.from_numpy(W.synth_hidden((n, h, w, k), seed=1007)).to(dev)
         bufs[k] = (x, o0, i0, torch.empty_like(x), torch.empty_like(x))
 
     def context(aux_name, k, nhwc, conv, dtype):
@@ -105,13 +121,13 @@ def main():
         ctx.set_circuit_variant(var)
         if nhwc and k == 64:
             ctx.set_nhwc_loop(True)
-        if conv == "fft":
-            ctx.set_nhwc_conv(L.MP_CN_CONV_FFT)
+        if conv != "direct":
+            ctx.set_nhwc_conv(L.NHWC_CONVS[conv])
         for v in table:
             ctx.set_weight(v.name, W.synth_value(v, 1234, T))
         ctx.finalize(L.dtype_code(dtype))
         assert ctx.info("channels") == k and ctx.info("nhwc_loop") == int(nhwc)
-        assert ctx.info("nhwc_conv") == int(conv == "fft")
+        assert ctx.info("nhwc_conv") == L.NHWC_CONVS[conv]      # 0 direct, 1 fft, 2 fft_tiled
         x, o0, i0, out, iout = bufs[k]
         return ctx, aux, lambda: ctx.circuit_fwd_var(x, o0, i0, out, iout, T, st, var)
 
@@ -138,7 +154,7 @@ def main():
             e1.record()
             e1.synchronize()
             times[k].append(e0.elapsed_time(e1))
-    res = {"tree": bench.tree_stamp(), "batch": n, "hw": [hw, hw], "ssf": a.ssf, "timesteps": T,
+    res = {"tree": bench.tree_stamp(), "batch": n, "hw": [h, w], "fft_tiles_per_image": ntile, "ssf": a.ssf, "timesteps": T,
            "dtype": {f[0]: f[4] for f in chosen},
            "runs": a.runs, "warmup": a.warmup, "device": torch.cuda.get_device_name(0), "forward_ms": {}}
     for k, ts in times.items():
@@ -153,7 +169,7 @@ def main():
         forms[f"{an}/k64_general"][2]()
         torch.cuda.synchronize()
         ref = out.clone()
-        for other in ("k64_nhwc", "k64_nhwc_fft", "k64_general_fft"):
+        for other in ("k64_nhwc", "k64_nhwc_fft", "k64_nhwc_fft_tiled", "k64_general_fft"):
             if f"{an}/{other}" in forms:
                 forms[f"{an}/{other}"][2]()
                 torch.cuda.synchronize()
@@ -181,11 +197,11 @@ def main():
         kk = {"launches_per_forward": cnts, "ms_per_forward": {key: round(v, 4) for key, v in fwd.items()},
               "profiled_forward_ms": round(total, 4),
               "conv_share_of_forward": round(sum(fwd[key] for key in CONV_KEYS) / total, 4)}
-        b_in, b_out = kernel_bytes(aux, n, hw, hw, k, T)
+        b_in, b_out = kernel_bytes(aux, n, h, w, k, T)
         rated = [("cn_in", b_in, T), ("cn_out", b_out, T)]
         if fwd["cn_spec_gemm"] > 0:
-            rated += [(key, nb, 2 * T) for key, nb in fft_conv_bytes(n, hw, hw, k, T).items()]
-            kk["cn_spec_gemm_TFLOPs_issued"] = round(fft_conv_flops(n, k, T) / (fwd["cn_spec_gemm"] * 1e-3) / 1e12, 2)
+            rated += [(key, nb, 2 * T) for key, nb in fft_conv_bytes(n, h, w, k, T, a.ssf).items()]
+            kk["cn_spec_gemm_TFLOPs_issued"] = round(fft_conv_flops(n * ntile, k, T) / (fwd["cn_spec_gemm"] * 1e-3) / 1e12, 2)
         for key, nbytes, launches in rated:
             gbps = nbytes / (fwd[key] * 1e-3) / 1e9
             kk[key] = {"ms_per_launch_p50": round(fwd[key] / launches, 4), "algorithmic_bytes_per_forward": nbytes,
