@@ -261,10 +261,7 @@ __global__ void pack_conv64x3_kernel(const float* __restrict__ w, f16x8* out, in
 
 // MP_CONV_DB=0: the single-buffered halo (A/B); the double-buffered one is used for the backbone
 static bool conv_db() {
-  static const int on = [] {
-    const char* e = std::getenv("MP_CONV_DB");
-    return e ? std::atoi(e) : 1;
-  }();
+  static const int on = env_int("MP_CONV_DB", 1);
   return on;
 }
 
@@ -294,10 +291,7 @@ constexpr int X3_NW = 8, X3_SCHED = 1;
 // 0.145 / 0.160 / -.  Hence 8 rows up to 128 workgroups of the 32-row tiling (B <= 32 at 64 x 64),
 // else 32.  MP_CONV_SMALL=0 keeps 32.
 static bool conv_small_tiles(const ConvArgs& a, int B) {
-  static const int on = [] {
-    const char* e = std::getenv("MP_CONV_SMALL");
-    return e ? std::atoi(e) : 1;
-  }();
+  static const int on = env_int("MP_CONV_SMALL", 1);
   return on && a.H % 8 == 0 && (long)B * (a.W / TW) * (a.H / TH3) <= 128;
 }
 

@@ -13,6 +13,7 @@
 #include "mp_kernels.hpp"
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <utility>
@@ -730,10 +731,7 @@ hipError_t launch_fc_gemm_x3(const float* A, int lda, const void* Wpk, float uns
 #define MP_FC_X3K(NPV, MBV, BKV)                                                                                   \
   hipLaunchKernelGGL((fc_gemm_x3_kernel<NPV, MBV, BKV>), dim3(grid), dim3(256), 0, st, A, lda, w, part, M, K, N32, \
                      kslice, unscale, S)
-  static const int bk64 = [] {
-    const char* e = std::getenv("MP_FC_BK64");
-    return e ? std::atoi(e) : 1;
-  }();
+  static const int bk64 = env_int("MP_FC_BK64", 1);
   // one product (bf16): 64-deep K steps, half the barriers and LDS staging passes per MFMA --
   // bf16 fc_1 0.320 -> 0.263 ms at batch 256, 0.161 -> 0.129 at 32, 0.153 -> 0.106 at 1
   if (nprod == 1 && bk64 && K % 64 == 0 && kslice % 64 == 0) {
@@ -773,13 +771,11 @@ int fc_choose_splits(int M, int K, int N, int* kslice) {
   // N = 512: 18 / 12 slices gave 192 / 128 blocks at batch 256 and 0.25 ms each).  A function of
   // K and N only, so a crop's sums group the same way at every batch.  MP_FC_KSLICE (A/B only)
   // fixes the slice length.
-  static const char* kenv = std::getenv("MP_FC_KSLICE");
-  static const int ksz = kenv ? std::max(32, std::atoi(kenv)) : 5440;
+  static const int kfix = env_int("MP_FC_KSLICE", INT_MIN);   // INT_MIN: unset (no atoi result)
+  static const bool kenv = kfix != INT_MIN;
+  static const int ksz = kenv ? std::max(32, kfix) : 5440;
   const int nt = ((N + 31) / 32 + 3) / 4;   // 128-column tiles
-  static const int smallk = [] {   // K per slice below 32k (A/B knob MP_FC_SMALLK)
-    const char* e = std::getenv("MP_FC_SMALLK");
-    return e ? std::max(32, std::atoi(e)) : 128;
-  }();
+  static const int smallk = std::max(32, env_int("MP_FC_SMALLK", 128));   // K per slice below 32k (A/B knob)
   int S = K >= 32768 ? std::max(1, K / ksz) : std::min(64, (K + smallk - 1) / smallk);
   if (K >= 32768 && !kenv) S = std::min(std::max(S, (384 + nt - 1) / nt), K / 512);
   // N a multiple of 256 (fc_1: 1,024): the 256 x 256 tiles of launch_fc_gemm_x3p's 256-row kernel,

@@ -884,10 +884,7 @@ __global__ __launch_bounds__(LF_NT, 1) void lfft_fwd_kernel(const float* __restr
 #define LFFT_MAXB 8   // largest batch for the latency kernels (profiles/r3y: B = 8 1.166 -> 1.126 ms, B = 16 1.354 -> 1.645); MP_LFFT_MAXB overrides, 0 = off
 #endif
 static int lfft_maxb() {
-  static const int v = [] {
-    const char* e = std::getenv("MP_LFFT_MAXB");
-    return e ? std::atoi(e) : LFFT_MAXB;
-  }();
+  static const int v = env_int("MP_LFFT_MAXB", LFFT_MAXB);
   return v;
 }
 
@@ -1434,10 +1431,7 @@ bool fft_c4_maps() { return (FFT_C4 & 2) != 0; }
 bool fft_c4_state() { return (FFT_C4 & 4) != 0; }
 bool fft_c4_drive() { return (FFT_C4 & 8) != 0; }
 bool fft_bf16_maps() {
-  static const bool v = [] {
-    const char* e = std::getenv("MP_BF16_MAPS");
-    return e ? std::atoi(e) != 0 : true;
-  }();
+  static const bool v = env_int("MP_BF16_MAPS", 1) != 0;
   return v;
 }
 size_t fft_spec_bytes(int B) { return (size_t)B * 16 * NF * 4 * sizeof(cpx); }

@@ -1403,10 +1403,7 @@ __global__ __launch_bounds__(512, 1) void col8p_bf_kernel(void* __restrict__ Zv,
 
 // ------------------------------------------------------------------------------------ launchers
 bool fft4_enabled() {
-  static const bool v = [] {
-    const char* e = std::getenv("MP_FFT4");
-    return e ? std::atoi(e) != 0 : true;
-  }();
+  static const bool v = env_int("MP_FFT4", 1) != 0;
   return v;
 }
 
@@ -1425,10 +1422,7 @@ bool fft4_enabled() {
 #define MAP_NT_MINB_BF 128
 #endif
 static bool map_nt(bool bf, int ntot) {
-  static const int v = [] {
-    const char* e = std::getenv("MP_MAP_NT");
-    return e ? (std::atoi(e) != 0 ? 1 : 0) : -1;
-  }();
+  static const int v = env_int("MP_MAP_NT", -1);
   return v < 0 ? ntot >= (bf ? MAP_NT_MINB_BF : MAP_NT_MINB) : v != 0;
 }
 
@@ -1443,10 +1437,7 @@ static bool map_nt(bool bf, int ntot) {
 // 6.04 -> 6.15, 7.87 -> 8.11, 2.368 -> 2.429; profiles/r6/ab/ab_map_nt.jsonl)
 static bool z_default_policy(bool bf, int B, int ntot) { return ntot <= 32 || (map_nt(bf, ntot) && B <= 64); }
 static bool col8_znt(bool bf, int B, int ntot) {
-  static const int v = [] {
-    const char* e = std::getenv("MP_COL8_ZNT");
-    return e ? (std::atoi(e) != 0 ? 1 : 0) : -1;
-  }();
+  static const int v = env_int("MP_COL8_ZNT", -1);
   return v < 0 ? !bf && !z_default_policy(bf, B, ntot) : v != 0;
 }
 
@@ -1455,37 +1446,26 @@ static bool col8_znt(bool bf, int B, int ntot) {
 // slices of 128) 8.00 vs 8.05 ms per forward with col8_kernel; B = 128 (slices of 64) 4.35 vs 4.23 --
 // a persistent launch holding every CU keeps the other slice's kernels off the chip until it ends
 static int col8p_minb() {
-  static const int v = [] {
-    const char* e = std::getenv("MP_COL8P");
-    return e ? std::atoi(e) : 128;
-  }();
+  static const int v = env_int("MP_COL8P", 128);
   return v;
 }
 // MP_COL8Q (default 0): 1 runs the software-pipelined form col8q_kernel instead of col8p_kernel (same
 // box, B = 256: 0.179 vs 0.170 ms; profiles/r6/ab/ab_col8.jsonl)
 static bool col8q_on() {
-  static const bool v = [] {
-    const char* e = std::getenv("MP_COL8Q");
-    return e ? std::atoi(e) != 0 : false;
-  }();
+  static const bool v = env_int("MP_COL8Q", 0) != 0;
   return v;
 }
 // MP_COL8P_BF (default 1): the bf16 path's slices of >= MP_COL8P images run col8p_bf_kernel
 static bool col8p_bf_on() {
-  static const bool v = [] {
-    const char* e = std::getenv("MP_COL8P_BF");
-    return e ? std::atoi(e) != 0 : true;
-  }();
+  static const bool v = env_int("MP_COL8P_BF", 1) != 0;
   return v;
 }
 static int col8p_blocks() {
   static const int v = [] {
-    const char* e = std::getenv("MP_COL8P_BLOCKS");
-    if (e) return std::max(1, std::atoi(e));
     int dev = 0, ncu = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return 256;
-    return std::max(1, ncu);
+      ncu = 256;
+    return std::max(1, env_int("MP_COL8P_BLOCKS", ncu));
   }();
   return v;
 }
@@ -1544,19 +1524,13 @@ hipError_t launch_col_gemm(void* Z, const void* Gc, int B, float unscale, hipStr
 // fp32 (interleaved same-box timing 8.27 -> 8.21 ms per B = 256 forward; profiles/r5o), off for bf16
 // (5.080 vs 5.079 ms); off where col8_znt is (z_default_policy)
 static bool row8_znt(bool bf, int B, int ntot) {
-  static const int v = [] {
-    const char* e = std::getenv("MP_ROW8_ZNT");
-    return e ? (std::atoi(e) != 0 ? 1 : 0) : -1;
-  }();
+  static const int v = env_int("MP_ROW8_ZNT", -1);
   return v < 0 ? !bf && !z_default_policy(bf, B, ntot) : v != 0;
 }
 
 // MP_ROWQ_MAXB: batch slices up to this many images run row A as rowq_a_kernel (fp32; default 8)
 static int rowq_maxb() {
-  static const int v = [] {
-    const char* e = std::getenv("MP_ROWQ_MAXB");
-    return e ? std::atoi(e) : 8;
-  }();
+  static const int v = env_int("MP_ROWQ_MAXB", 8);
   return v;
 }
 

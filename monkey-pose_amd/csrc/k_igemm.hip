@@ -1432,11 +1432,6 @@ hipError_t launch_igemm_conv(const IgemmArgs& a, hipStream_t st) {
 }
 
 namespace {
-int env_flag(const char* name, int dflt) {
-  const char* e = std::getenv(name);
-  return e ? std::atoi(e) : dflt;
-}
-
 // halo tiles: stride 1, SAME, odd KS in {3, 5}, Cin % 32 == 0, tiles of whole rows of one image (or
 // whole images), halo within HX_ITEMS per thread and two buffers within 80 KiB
 // channels per staged chunk of the halo kernel: 32 unless the weights are padded to a multiple of 16
@@ -1444,7 +1439,7 @@ int env_flag(const char* name, int dflt) {
 int halo_ch(const IgemmArgs& a) { return (a.Cin % 32 == 0 || a.cinp % 32 == 0) ? 32 : 16; }
 
 bool halo_geom(const IgemmArgs& a, HaloGeom& hg, size_t& lds) {
-  static const int halo = env_flag("MP_IGEMM_HALO", 1);
+  static const int halo = env_int("MP_IGEMM_HALO", 1);
   if (!(halo && a.stride == 1 && (a.KS == 3 || a.KS == 5) && a.pad_t == a.KS / 2 && a.pad_l == a.KS / 2 &&
         a.Ho == a.H && a.Wo == a.W && a.ldx % 4 == 0 && a.cix % 4 == 0 && a.W <= IG_BM &&
         (a.Cin % 32 == 0 || (a.wpad && a.cinp % 16 == 0 && a.cinp >= a.Cin && a.Cin % 4 == 0)) &&
@@ -1478,7 +1473,7 @@ bool halo_geom(const IgemmArgs& a, HaloGeom& hg, size_t& lds) {
 // 8x8 maps, 28 % padding, slower -- a position-major tile gathers 128 images' pixels and loses the
 // neighbouring-pixel input reuse of a row-major tile)
 bool pm_path(const IgemmArgs& a) {
-  static const int tapskip = env_flag("MP_IGEMM_TAPSKIP", 1);
+  static const int tapskip = env_int("MP_IGEMM_TAPSKIP", 1);
   if (!(tapskip && a.KS > 1 && a.Ho * a.Wo <= 64 && a.Cin % IG_BK == 0)) return false;
   long valid = 0;
   for (int y = 0; y < a.Ho; ++y)
@@ -1492,7 +1487,7 @@ bool pm_path(const IgemmArgs& a) {
 }
 
 bool wide_path(const IgemmArgs& a) {
-  static const int wide = env_flag("MP_IGEMM_WIDE", 1);
+  static const int wide = env_int("MP_IGEMM_WIDE", 1);
   return wide && (a.Cout + 31) / 32 >= 3;   // Cout > 64: 2 x 2 wave tiles, weights staged in LDS
 }
 }  // namespace
@@ -1502,7 +1497,7 @@ int igemm_pm_splits(const IgemmArgs& a) {
   // 256 blocks of 128 x 128 otherwise: one wave per SIMD) 0.76 -> 0.40 ms on one stream (4 splits
   // 0.42, 16 splits 0.43), and on the graph runtime's streams hier fp32 34.5k -> 37.7k crops/s,
   // bf16 53.0k -> 56.3k (round 1 had measured 4 splits slower there; MP_IGEMM_PM_SPLITS=1 for A/B)
-  static const int maxs = std::max(1, env_flag("MP_IGEMM_PM_SPLITS", 8));
+  static const int maxs = std::max(1, env_int("MP_IGEMM_PM_SPLITS", 8));
   if (a.K < 4 || !wide_path(a)) return 1;
   HaloGeom hg;
   size_t lds;
@@ -1517,7 +1512,7 @@ int igemm_pm_splits(const IgemmArgs& a) {
 // 32 pixel tiles x 2 cout tiles = 64 blocks at B = 256 otherwise).  A property of the layer alone
 // (K, map size), never of the batch.
 int igemm_x3w_splits(const IgemmArgs& a) {
-  static const int on = env_flag("MP_IGEMM_SMALL_SPLITK", 1);
+  static const int on = env_int("MP_IGEMM_SMALL_SPLITK", 1);
   if (!on || !wide_path(a) || a.Ho * a.Wo > 16 || pm_path(a)) return 1;
   HaloGeom hg;
   size_t lds;
@@ -1546,7 +1541,7 @@ IgemmPath x3_path(const IgemmArgs& a, HaloGeom& hg, size_t& lds) {
   IgemmPath p;
   p.pool = a.pool;
   const int N32 = (a.Cout + 31) / 32;
-  static const int pw = env_flag("MP_IGEMM_PW", 1);
+  static const int pw = env_int("MP_IGEMM_PW", 1);
   if (pw && a.KS == 1 && a.stride == 1 && a.Ho == a.H && a.Wo == a.W && a.pad_t == 0 && a.pad_l == 0 &&
       a.K == a.Cin && a.K <= 192 && a.Cin % 4 == 0 && a.cix % 4 == 0 && a.ldx % 4 == 0 && N32 <= 8 && !a.pool) {
     p.nch = std::min(6, (a.K + 31) / 32);
@@ -1555,7 +1550,7 @@ IgemmPath x3_path(const IgemmArgs& a, HaloGeom& hg, size_t& lds) {
     // 0.420 ms); 2 = also 2 / 3, where the grid idles or clamps waves (conv_4_1_1x1 0.195 -> 0.176,
     // conv_3_1_1x1 0.127 -> 0.114, profiles/r3zp); 3 (default) = also 4 (conv_5_1_1x1 0.294 -> 0.254,
     // profiles/r3zw)
-    static const int pwn = env_flag("MP_IGEMM_PWN", 3);
+    static const int pwn = env_int("MP_IGEMM_PWN", 3);
     if ((pwn && (N32 == 5 || N32 == 6) && p.nch >= 4) || (pwn >= 2 && (N32 == 2 || N32 == 3)) ||
         (pwn == 3 && N32 == 4)) {
       p.family = MP_PATH_PWN;
@@ -1568,14 +1563,14 @@ IgemmPath x3_path(const IgemmArgs& a, HaloGeom& hg, size_t& lds) {
   // halo tiles for Cout > 64, and (MP_IGEMM_HALO_NARROW, on by default) for Cout <= 64 with the
   // four waves along the pixels (igemm_x3h_kernel<.., NARROW>): the im2col kernel gathers every
   // input element KS^2 times
-  static const int narrow = env_flag("MP_IGEMM_HALO_NARROW", 1);
+  static const int narrow = env_int("MP_IGEMM_HALO_NARROW", 1);
   // (zero-padded Cin costs MFMAs: Cin = 12 padded to 32 was 2.7x and lost; the narrow halo path is
   // taken where the padded channels are at most 4/3 of Cin -- 16-channel chunks make that 12 -> 16,
   // 24 -> 32, 40 / 48 -> 48)
   if ((wide_path(a) || (narrow && (a.Cin % 32 == 0 || 3 * (a.cinp ? a.cinp : a.Cin) <= 4 * a.Cin))) &&
       halo_geom(a, hg, lds)) {
-    static const int tall = env_flag("MP_IGEMM_HALO_TALL", 1);
-    static const int narrow1 = env_flag("MP_IGEMM_HALO_NARROW1", 1);
+    static const int tall = env_int("MP_IGEMM_HALO_TALL", 1);
+    static const int narrow1 = env_int("MP_IGEMM_HALO_NARROW1", 1);
     p.family = MP_PATH_HALO;
     p.ks = a.KS == 3 ? 3 : 5;
     p.ch = 32;
@@ -1629,7 +1624,7 @@ hipError_t launch_igemm_x3(const IgemmArgs& a, const void* wpk, float unscale, h
   const int N32 = (a.Cout + 31) / 32;
   const f16x8* w = static_cast<const f16x8*>(wpk);
   const bool one = a.nprod == 1;   // MP_DTYPE_BF16: one f16 product per MAC
-  static const int xcd = env_flag("MP_IGEMM_XCD", 1);
+  static const int xcd = env_int("MP_IGEMM_XCD", 1);
   HaloGeom hg;
   size_t lds = 0;
   const IgemmPath path = x3_path(a, hg, lds);

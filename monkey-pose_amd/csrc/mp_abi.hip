@@ -359,13 +359,12 @@ void ensure_ws(mp_ctx* c, int64_t n, int64_t H, int64_t W) {
     c->bufA.alloc(st);
     c->bufB.alloc(st);
     c->fcin.alloc(st);
+    // the head's split-K partials (pose_fwd head): fc_1's in part, fc_out's in part2
     int ks;
     const int S = fc_choose_splits((int)nb, c->fc1_in, c->fc1_out, &ks);
-    const size_t p1 = (size_t)S * nb * ((c->fc1_out + 31) / 32 * 32) * sizeof(float);
+    c->part.alloc((size_t)S * nb * ((c->fc1_out + 31) / 32 * 32) * sizeof(float));
     const int S2 = fc_choose_splits((int)nb, c->fc1_out, c->nout, &ks);
-    const size_t p2 = (size_t)S2 * nb * ((c->nout + 31) / 32 * 32) * sizeof(float);
-    c->part.alloc(std::max(p1, p2));
-    c->part2.alloc(p2);
+    c->part2.alloc((size_t)S2 * nb * ((c->nout + 31) / 32 * 32) * sizeof(float));
     c->h1.alloc((size_t)nb * c->fc1_out * sizeof(float));
   }
   (void)px;
@@ -388,38 +387,6 @@ void eCRF_conv(mp_ctx* c, int epi, const ConvArgs& a, int n, hipStream_t st) {
     hip_check(launch_conv64(c->ssf, epi, a, n, st), "conv15");
 }
 
-// FFT path of one hGRU step (k_fft.hip): the A half-step's inverse transform, its epilogue and the
-// B half-step's forward transform are one kernel, so per step:
-//   fft_fwd(Og) -> S;  spec_gemm -> Y;  inv_a_fwd: I = A-epi(IFFT(Y)), S = FFT(I);
-//   spec_gemm -> Y;  fft_inv -> P2;  epi_b(P2, I, O) -> O', Og'
-void fft_step(mp_ctx* c, const ConvArgs& a, const ConvArgs& b, int n, hipStream_t st) {
-  const bool bf = c->dtype == MP_DTYPE_BF16;
-  {
-    ProfScope pa(c, st, "conv15_a");
-    {
-      ProfScope ps(c, st, "fft_fwd");
-      hip_check(launch_fft_fwd(a.src, c->specS.p, n, a.H, a.W, st, bf), "fft_fwd");
-    }
-    {
-      ProfScope ps(c, st, "spec_gemm");
-      hip_check(launch_spec_gemm(c->specS.p, c->spec_g.p, c->specY.p, n, c->p_unscale, st, bf), "spec_gemm");
-    }
-    ProfScope ps(c, st, "inv_a_fwd");
-    hip_check(launch_fft_inv_a_fwd(c->specY.p, a, c->specS.p, n, st, bf), "fft_inv_a_fwd");
-  }
-  ProfScope pb(c, st, "conv15_b");
-  {
-    ProfScope ps(c, st, "spec_gemm");
-    hip_check(launch_spec_gemm(c->specS.p, c->spec_g.p, c->specY.p, n, c->p_unscale, st, bf), "spec_gemm");
-  }
-  {
-    ProfScope ps(c, st, "fft_inv");
-    hip_check(launch_fft_inv(c->specY.p, c->specP.f(), n, b.H, b.W, st, bf), "fft_inv");
-  }
-  ProfScope ps(c, st, "epi_b");
-  hip_check(launch_spec_epi_b(b, c->specP.f(), c->or_x3.p, c->or_us, c->ir_x3.p, c->ir_us, n, st, bf), "B epilogue");
-}
-
 // map-size rule of the context's association-field conv path (MP_ERR_SHAPE otherwise)
 void check_map(mp_ctx* c, int64_t H, int64_t W, const char* what) {
   if (is_fft(c->dtype)) {
@@ -440,6 +407,19 @@ struct StateOut {
   float* I = nullptr;
   int T = 0;
 };
+
+// the loops' state-output argument: the two stacks of a T-step forward, NULL where neither is wanted
+const StateOut* state_out(StateOut& so, float* O, float* I, int T) {
+  so.O = O;
+  so.I = I;
+  so.T = T;
+  return (O || I) ? &so : nullptr;
+}
+
+// a map's pointer m elements in, in units of its element type: bf16 (k_fft.hip map_ld4) or fp32
+float* map_at(const DevBuf& buf, size_t m, bool bf16) {
+  return bf16 ? reinterpret_cast<float*>(static_cast<uint16_t*>(buf.p) + m) : buf.f() + m;
+}
 
 // copy step t's O / I maps (C8, bf16 under MP_DTYPE_BF16 maps; ic4: I is the FFT loop's C4 map) of images
 // [b0, b0 + n) into the stacks
@@ -473,76 +453,122 @@ void final_out(ConvArgs& b, float* final_dst2, const SplitOut* sp, int b0, int H
   }
 }
 
-// the hGRU loop of images [b0, b0 + n) on stream st (FFT path), all state pointers offset
-void fft_circuit_range(mp_ctx* c, int b0, int n, int H, int W, int T, float* final_dst2, const StateOut* so,
-                       const SplitOut* sp, hipStream_t st) {
-  const size_t m = (size_t)b0 * 64 * H * W;              // elements per image of a C8 / NHWC map
-  void* S = static_cast<char*>(c->specS.p) + fft_spec_bytes(b0);
-  void* Y = static_cast<char*>(c->specY.p) + fft_spec_bytes(b0);
-  // maps X, O, I, Og, P2 (bf16 under MP_DTYPE_BF16, k_fft.hip map_ld4): the same element offset,
-  // in units of their element type; the NHWC output stays fp32
-  const bool bm = bf16_maps(c);
-  auto map = [&](DevBuf& buf) { return bm ? reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(buf.p) + m) : buf.f() + m; };
-  float* P = map(c->specP);
-  for (int t = 0; t < T; ++t) {
-    ConvArgs a{};
-    a.H = H;
-    a.W = W;
-    a.src = map(c->Og);
-    a.dst = map(c->I);
-    a.X = map(c->X);
-    a.O = map(c->O);
-    a.vecs = c->vecs.f();
-    ConvArgs b{};
-    b.H = H;
-    b.W = W;
-    b.dst = map(c->O);
-    b.O = map(c->O);
-    b.I = map(c->I);
-    b.vecs = c->vecs.f();
-    b.rho = c->rho[t];
-    b.mode = 0;
-    b.dst2 = map(c->Og);
-    if (t == T - 1) final_out(b, final_dst2, sp, b0, H, W);
-    const bool bf = c->dtype == MP_DTYPE_BF16;
-    hip_check(launch_fft_fwd(a.src, S, n, H, W, st, bf), "fft_fwd");
-    hip_check(launch_spec_gemm(S, c->spec_g.p, Y, n, c->p_unscale, st, bf), "spec_gemm");
-    hip_check(launch_fft_inv_a_fwd(Y, a, S, n, st, bf), "fft_inv_a_fwd");
-    hip_check(launch_spec_gemm(S, c->spec_g.p, Y, n, c->p_unscale, st, bf), "spec_gemm");
-    hip_check(launch_fft_inv(Y, P, n, H, W, st, bf), "fft_inv");
-    hip_check(launch_spec_epi_b(b, P, c->or_x3.p, c->or_us, c->ir_x3.p, c->ir_us, n, st, bf), "B epilogue");
-    store_step(so, b.O, b.I, b0, n, H, W, t, bm, st, fft_c4_maps(), fft_c4_state());
-  }
-}
-
 // MP_O0_DIRECT (default 1): the fp32 four-step loop's first step reads O0 (NHWC) directly; 0: row(INIT)
 // copies it into the C8 state map first (1 MB per image more)
 bool o0_direct() {
-  static const bool v = [] {
-    const char* e = std::getenv("MP_O0_DIRECT");
-    return e ? std::atoi(e) != 0 : true;
-  }();
+  static const bool v = env_int("MP_O0_DIRECT", 1) != 0;
   return v;
 }
 
-// the hGRU loop of images [b0, b0 + n) on stream st, four-step FFT path (k_fft4.hip): one row(INIT)
-// (hgru_module.py:696-711 on O0, and the forward transform of the gated state), then per timestep
+// the A / B half-steps' arguments of one timestep on the maps X, O, I and Og (the gated state, the conv
+// input of every loop but the four-step one, which keeps it on chip: Og NULL); the direct convs also
+// take their input, the packed p_r and the B epilogue's gate weights from here
+struct StepArgs {
+  ConvArgs a{}, b{};
+};
+StepArgs step_args(mp_ctx* c, int H, int W, float* X, float* O, float* I, float* Og, float rho) {
+  StepArgs s;
+  ConvArgs &a = s.a, &b = s.b;
+  a.H = b.H = H;
+  a.W = b.W = W;
+  a.vecs = b.vecs = c->vecs.f();
+  a.X = X;
+  a.O = b.O = O;
+  a.dst = I;
+  b.I = I;
+  b.dst = O;
+  b.rho = rho;
+  b.mode = 0;
+  if (Og) {
+    a.src = Og;
+    b.dst2 = Og;
+  }
+  if (!is_fft(c->dtype)) {
+    a.wpk = b.wpk = c->p_pk.v4();
+    b.src = I;
+    b.gpk_or = c->or_pk.v4();
+    b.gpk_ir = c->ir_pk.v4();
+  }
+  return s;
+}
+
+// one step of the four-step FFT loop (k_fft4.hip), every launch in place on one spectrum-sized buffer Z:
 //   col -> row A (I = tanh(X - (beta O + nu) P1), hgru_module.py:797-799) -> col -> row B (O', the
 //   next gated state; the last step: O' and BN_3(O_T))
-// every launch in place on one spectrum-sized buffer Z
 // ntot: the forward's whole batch (its cache policy: k_fft4.hip col8_znt, row8_znt, map_nt)
-void fft4_circuit_range(mp_ctx* c, int b0, int n, int ntot, int H, int W, int T, const float* o0_nhwc,
-                        float* final_dst2, const StateOut* so, const SplitOut* sp, hipStream_t st) {
-  const size_t m = (size_t)b0 * 64 * H * W;
-  const bool bf = c->dtype == MP_DTYPE_BF16;   // bf16 Z (half a spectrum's bytes per image) and maps
-  void* Z = static_cast<char*>(c->specS.p) + fft_spec_bytes(b0) / (bf ? 2 : 1);
-  auto map = [&](DevBuf& buf) { return bf ? reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(buf.p) + m) : buf.f() + m; };
-  float* X = map(c->X);
-  float* O = map(c->O);
-  float* I = map(c->I);
-  // fp32: step 0's row A / B read O0 itself (NHWC) instead of a C8 copy that row(INIT) would write
-  const bool o0d = !bf && o0_direct();
+void four_step(mp_ctx* c, void* Z, const ConvArgs& a, const ConvArgs& b, bool last, int n, int ntot, hipStream_t st) {
+  const bool bf = c->dtype == MP_DTYPE_BF16;
   {
+    ProfScope pa(c, st, "conv15_a");
+    {
+      ProfScope ps(c, st, "col_gemm");
+      hip_check(launch_col_gemm(Z, c->spec_g.p, n, c->p_unscale, st, bf, ntot), "col_gemm");
+    }
+    ProfScope ps(c, st, "row_a");
+    hip_check(launch_row(0, Z, a, c->or_x3.p, c->or_us, c->ir_x3.p, c->ir_us, nullptr, n, st, bf, ntot), "row_a");
+  }
+  ProfScope pb(c, st, "conv15_b");
+  {
+    ProfScope ps(c, st, "col_gemm");
+    hip_check(launch_col_gemm(Z, c->spec_g.p, n, c->p_unscale, st, bf, ntot), "col_gemm");
+  }
+  ProfScope ps(c, st, last ? "row_final" : "row_b");
+  hip_check(launch_row(last ? 2 : 1, Z, b, c->or_x3.p, c->or_us, c->ir_x3.p, c->ir_us, nullptr, n, st, bf, ntot),
+            last ? "row_final" : "row_b");
+}
+
+// one step of the six-launch FFT loop (k_fft.hip): the A half-step's inverse transform, its epilogue and
+// the B half-step's forward transform are one kernel, so per step:
+//   fft_fwd(Og) -> S;  spec_gemm -> Y;  inv_a_fwd: I = A-epi(IFFT(Y)), S = FFT(I);
+//   spec_gemm -> Y;  fft_inv -> P2;  epi_b(P2, I, O) -> O', Og'
+void six_launch(mp_ctx* c, void* S, void* Y, float* P, const ConvArgs& a, const ConvArgs& b, int n, hipStream_t st) {
+  const bool bf = c->dtype == MP_DTYPE_BF16;
+  {
+    ProfScope pa(c, st, "conv15_a");
+    {
+      ProfScope ps(c, st, "fft_fwd");
+      hip_check(launch_fft_fwd(a.src, S, n, a.H, a.W, st, bf), "fft_fwd");
+    }
+    {
+      ProfScope ps(c, st, "spec_gemm");
+      hip_check(launch_spec_gemm(S, c->spec_g.p, Y, n, c->p_unscale, st, bf), "spec_gemm");
+    }
+    ProfScope ps(c, st, "inv_a_fwd");
+    hip_check(launch_fft_inv_a_fwd(Y, a, S, n, st, bf), "fft_inv_a_fwd");
+  }
+  ProfScope pb(c, st, "conv15_b");
+  {
+    ProfScope ps(c, st, "spec_gemm");
+    hip_check(launch_spec_gemm(S, c->spec_g.p, Y, n, c->p_unscale, st, bf), "spec_gemm");
+  }
+  {
+    ProfScope ps(c, st, "fft_inv");
+    hip_check(launch_fft_inv(Y, P, n, b.H, b.W, st, bf), "fft_inv");
+  }
+  ProfScope ps(c, st, "epi_b");
+  hip_check(launch_spec_epi_b(b, P, c->or_x3.p, c->or_us, c->ir_x3.p, c->ir_us, n, st, bf), "B epilogue");
+}
+
+// the hGRU loop of images [b0, b0 + n) of a forward of ntot on stream st, every state pointer offset: the
+// four-step or the six-launch FFT loop, or the direct convs (whole batch only).  The four-step loop begins
+// with one row(INIT) (hgru_module.py:696-711 on O0, and the forward transform of the gated state); the
+// other loops' gate_init is the caller's, for the whole batch
+void circuit_range(mp_ctx* c, int b0, int n, int ntot, int H, int W, int T, const float* o0_nhwc, float* final_dst2,
+                   const StateOut* so, const SplitOut* sp, hipStream_t st) {
+  const bool fft = is_fft(c->dtype), bf = c->dtype == MP_DTYPE_BF16;
+  const size_t m = (size_t)b0 * 64 * H * W;   // elements per image of a C8 / NHWC map
+  // maps X, O, I, Og, P2 (bf16 under MP_DTYPE_BF16): the same element offset, in units of their element
+  // type; the NHWC output stays fp32.  The four-step loop has no Og, Y or P2, and a bf16 Z (half a
+  // spectrum's bytes per image)
+  const bool bm = bf16_maps(c);
+  float *X = map_at(c->X, m, bm), *O = map_at(c->O, m, bm), *I = map_at(c->I, m, bm);
+  float* Og = c->fft4 ? nullptr : map_at(c->Og, m, bm);
+  float* P = fft && !c->fft4 ? map_at(c->specP, m, bm) : nullptr;
+  void* S = fft ? static_cast<char*>(c->specS.p) + fft_spec_bytes(b0) / (c->fft4 && bf ? 2 : 1) : nullptr;
+  void* Y = fft && !c->fft4 ? static_cast<char*>(c->specY.p) + fft_spec_bytes(b0) : nullptr;
+  // fp32: step 0's row A / B read O0 itself (NHWC) instead of a C8 copy that row(INIT) would write
+  const bool o0d = c->fft4 && !bf && o0_direct();
+  if (c->fft4) {
     ConvArgs a0{};
     a0.H = H;
     a0.W = W;
@@ -550,64 +576,36 @@ void fft4_circuit_range(mp_ctx* c, int b0, int n, int ntot, int H, int W, int T,
     a0.vecs = c->vecs.f();
     ProfScope pa(c, st, "conv15_a");
     ProfScope ps(c, st, "row_init");
-    hip_check(launch_row(3, Z, a0, c->or_x3.p, c->or_us, c->ir_x3.p, c->ir_us, o0_nhwc + m, n, st, bf, ntot), "row_init");
+    hip_check(launch_row(3, S, a0, c->or_x3.p, c->or_us, c->ir_x3.p, c->ir_us, o0_nhwc + m, n, st, bf, ntot), "row_init");
   }
   for (int t = 0; t < T; ++t) {
-    ConvArgs a{};
-    a.H = H;
-    a.W = W;
-    a.X = X;
-    a.O = O;
-    a.dst = I;
-    a.vecs = c->vecs.f();
-    ConvArgs b{};
-    b.H = H;
-    b.W = W;
-    b.I = I;
-    b.O = O;
-    b.dst = O;
-    if (o0d && t == 0) {
-      a.O = b.O = o0_nhwc + m;
-      a.o_nhwc = b.o_nhwc = 1;
-    }
-    b.vecs = c->vecs.f();
-    b.rho = c->rho[t];
-    b.mode = 0;
+    StepArgs s = step_args(c, H, W, X, O, I, Og, c->rho[t]);
     const bool last = t == T - 1;
-    if (last) {
-      final_out(b, final_dst2, sp, b0, H, W);
-      if (!so) b.dst = nullptr;   // O_T is read by nothing but BN_3 (row FINAL): no C8 map write
-    }
-    {
-      ProfScope pa(c, st, "conv15_a");
-      {
-        ProfScope ps(c, st, "col_gemm");
-        hip_check(launch_col_gemm(Z, c->spec_g.p, n, c->p_unscale, st, bf, ntot), "col_gemm");
+    if (last) final_out(s.b, final_dst2, sp, b0, H, W);
+    if (c->fft4) {
+      if (o0d && t == 0) {
+        s.a.O = s.b.O = o0_nhwc + m;
+        s.a.o_nhwc = s.b.o_nhwc = 1;
       }
-      ProfScope ps(c, st, "row_a");
-      hip_check(launch_row(0, Z, a, c->or_x3.p, c->or_us, c->ir_x3.p, c->ir_us, nullptr, n, st, bf, ntot), "row_a");
-    }
-    {
-      ProfScope pb(c, st, "conv15_b");
+      if (last && !so) s.b.dst = nullptr;   // O_T is read by nothing but BN_3 (row FINAL): no C8 map write
+      four_step(c, S, s.a, s.b, last, n, ntot, st);
+    } else if (fft) {
+      six_launch(c, S, Y, P, s.a, s.b, n, st);
+    } else {
       {
-        ProfScope ps(c, st, "col_gemm");
-        hip_check(launch_col_gemm(Z, c->spec_g.p, n, c->p_unscale, st, bf, ntot), "col_gemm");
+        ProfScope ps(c, st, "conv15_a");
+        eCRF_conv(c, EPI_HGRU_A, s.a, n, st);
       }
-      ProfScope ps(c, st, last ? "row_final" : "row_b");
-      hip_check(launch_row(last ? 2 : 1, Z, b, c->or_x3.p, c->or_us, c->ir_x3.p, c->ir_us, nullptr, n, st, bf, ntot),
-                last ? "row_final" : "row_b");
+      ProfScope ps(c, st, "conv15_b");
+      eCRF_conv(c, EPI_HGRU_B, s.b, n, st);
     }
-    store_step(so, O, I, b0, n, H, W, t, bf, st, fft_c4_maps(), fft_c4_state());
+    store_step(so, O, I, b0, n, H, W, t, bm, st, fft && fft_c4_maps(), fft && fft_c4_state());
   }
 }
 
-
 // fc_1 on pre-split activation planes (MP_FC_PRESPLIT=0: the fp32 map + in-loop split, for A/B)
 bool fc_presplit() {
-  static const bool v = [] {
-    const char* e = std::getenv("MP_FC_PRESPLIT");
-    return e ? std::atoi(e) != 0 : true;
-  }();
+  static const bool v = env_int("MP_FC_PRESPLIT", 1) != 0;
   return v;
 }
 
@@ -616,46 +614,31 @@ bool fc_presplit() {
 // the join.  Bit-identical, but each slice streams fc_1's 1.07 GB of weights: same box, B = 256 8.16 vs
 // 7.97 ms, B = 64 2.60 vs 2.36 (profiles/r6/ab/ab_fc_slice.jsonl)
 bool fc_slice() {
-  static const bool v = [] {
-    const char* e = std::getenv("MP_FC_SLICE");
-    return e ? std::atoi(e) != 0 : false;
-  }();
+  static const bool v = env_int("MP_FC_SLICE", 0) != 0;
   return v;
 }
 
 int stream_count() {
-  static const int v = [] {
-    const char* e = std::getenv("MP_STREAMS");
-    return e ? std::max(1, std::min(4, std::atoi(e))) : 2;
-  }();
+  static const int v = std::max(1, std::min(4, env_int("MP_STREAMS", 2)));
   return v;
 }
 
 // MP_BB_PIPE (default 1): the backbone per batch slice on the slice's stream; 0: whole batch first
 bool bb_pipeline() {
-  static const bool v = [] {
-    const char* e = std::getenv("MP_BB_PIPE");
-    return e ? std::atoi(e) != 0 : true;
-  }();
+  static const bool v = env_int("MP_BB_PIPE", 1) != 0;
   return v;
 }
 
 // MP_BB_STAGGER (default 1): a slice's backbone waits for the previous slice's, so that it overlaps that
 // slice's hGRU loop instead of the other backbone (same box, B = 256: 8.40 -> 8.28 ms; profiles/r5n)
 bool bb_stagger() {
-  static const bool v = [] {
-    const char* e = std::getenv("MP_BB_STAGGER");
-    return e ? std::atoi(e) != 0 : true;
-  }();
+  static const bool v = env_int("MP_BB_STAGGER", 1) != 0;
   return v;
 }
 
 // smallest batch slice worth a stream of its own (MP_SLICE_MIN, A/B knob)
 int slice_min() {
-  static const int v = [] {
-    const char* e = std::getenv("MP_SLICE_MIN");
-    return e ? std::max(1, std::atoi(e)) : 32;
-  }();
+  static const int v = std::max(1, env_int("MP_SLICE_MIN", 32));
   return v;
 }
 
@@ -672,17 +655,27 @@ void run_circuit(mp_ctx* c, int64_t n, int H, int W, int T, const float* o0_nhwc
   // their latency-bound kernels overlap (the per-kernel HIP-event profile keeps one stream)
   const int ns = std::min<int>(stream_count(), (int)(n / slice_min()));
   const bool multi = is_fft(c->dtype) && !c->prof && ns >= 2;
-  if (pre && !multi) (*pre)(0, (int)n, st);
-  if (c->fft4 && !multi) {
-    fft4_circuit_range(c, 0, (int)n, (int)n, H, W, T, o0_nhwc, final_dst2, so, sp, st);
-    if (post) (*post)(0, (int)n, st);
-    return;
-  }
-  if (multi) {
-    if (!c->fft4)
-      hip_check(launch_gate_init_x3(o0_nhwc, c->O.f(), c->Og.f(), c->ir_x3.p, c->ir_us, c->vecs.f(), (int)n, H, W,
-                                  st, c->dtype == MP_DTYPE_BF16),
+  // O0 -> O and the first gated state Og: one whole-batch launch on st (the four-step loop's row(INIT)
+  // does both per slice)
+  auto gate_init = [&] {
+    if (c->fft4) return;
+    hip_check(is_fft(c->dtype)
+                  ? launch_gate_init_x3(o0_nhwc, c->O.f(), c->Og.f(), c->ir_x3.p, c->ir_us, c->vecs.f(), (int)n, H, W, st,
+                                        c->dtype == MP_DTYPE_BF16)
+                  : launch_gate_init(o0_nhwc, c->O.f(), c->Og.f(), c->ir_pk.v4(), c->vecs.f(), (int)n, H, W, st),
               "gate_init");
+  };
+  // the slices: the whole batch on st, or ns runs of whole GEMM groups, the first on st and the others
+  // on side streams forked from it here and joined to it at the end
+  struct Slice {
+    int b0, cnt;
+    hipStream_t s;
+  };
+  std::vector<Slice> slices;
+  if (!multi) {
+    slices.push_back({0, (int)n, st});
+  } else {
+    gate_init();
     while ((int)c->sides.size() < ns - 1) {
       hipStream_t s;
       hipEvent_t e;
@@ -700,101 +693,54 @@ void run_circuit(mp_ctx* c, int64_t n, int H, int W, int T, const float* o0_nhwc
     for (int k = 0; k < ns; ++k) {
       const int g = groups / ns + (k < groups % ns ? 1 : 0);
       const int cnt = std::min<int>(g * gs, (int)n - b0);
-      hipStream_t s = k == 0 ? st : c->sides[k - 1];
-      if (k > 0) hip_check(hipStreamWaitEvent(s, c->ev_fork, 0), "hipStreamWaitEvent");
-      if (pre && bb_stagger() && k > 0) {   // slice k's backbone after slice k - 1's
-        if (!c->ev_pre) hip_check(hipEventCreateWithFlags(&c->ev_pre, hipEventDisableTiming), "hipEventCreate");
-        hip_check(hipStreamWaitEvent(s, c->ev_pre, 0), "hipStreamWaitEvent");
-      }
-      if (pre) (*pre)(b0, cnt, s);
-      if (pre && bb_stagger() && k + 1 < ns) {
-        if (!c->ev_pre) hip_check(hipEventCreateWithFlags(&c->ev_pre, hipEventDisableTiming), "hipEventCreate");
-        hip_check(hipEventRecord(c->ev_pre, s), "hipEventRecord");
-      }
-      if (c->fft4)
-        fft4_circuit_range(c, b0, cnt, (int)n, H, W, T, o0_nhwc, final_dst2, so, sp, s);
-      else
-        fft_circuit_range(c, b0, cnt, H, W, T, final_dst2, so, sp, s);
-      if (post) (*post)(b0, cnt, s);
+      slices.push_back({b0, cnt, k == 0 ? st : c->sides[k - 1]});
       b0 += cnt;
     }
-    for (int k = 1; k < ns; ++k) {
-      hip_check(hipEventRecord(c->ev_join[k - 1], c->sides[k - 1]), "hipEventRecord");
-      hip_check(hipStreamWaitEvent(st, c->ev_join[k - 1], 0), "hipStreamWaitEvent");
-    }
-    return;
   }
-  hip_check(is_fft(c->dtype)
-                ? launch_gate_init_x3(o0_nhwc, c->O.f(), c->Og.f(), c->ir_x3.p, c->ir_us, c->vecs.f(), (int)n, H, W, st,
-                                      c->dtype == MP_DTYPE_BF16)
-                : launch_gate_init(o0_nhwc, c->O.f(), c->Og.f(), c->ir_pk.v4(), c->vecs.f(), (int)n, H, W, st),
-            "gate_init");
-  for (int t = 0; t < T; ++t) {
-    ConvArgs a{};
-    a.H = H;
-    a.W = W;
-    a.src = c->Og.f();
-    a.wpk = c->p_pk.v4();
-    a.dst = c->I.f();
-    a.X = c->X.f();
-    a.O = c->O.f();
-    a.vecs = c->vecs.f();
-    ConvArgs b{};
-    b.H = H;
-    b.W = W;
-    b.src = c->I.f();
-    b.wpk = c->p_pk.v4();
-    b.dst = c->O.f();
-    b.O = c->O.f();
-    b.I = c->I.f();
-    b.vecs = c->vecs.f();
-    b.gpk_or = c->or_pk.v4();
-    b.gpk_ir = c->ir_pk.v4();
-    b.rho = c->rho[t];
-    b.mode = 0;
-    b.dst2 = c->Og.f();
-    if (t == T - 1) final_out(b, final_dst2, sp, 0, H, W);
-    if (is_fft(c->dtype)) {
-      fft_step(c, a, b, (int)n, st);
-    } else {
-      {
-        ProfScope ps(c, st, "conv15_a");
-        eCRF_conv(c, EPI_HGRU_A, a, (int)n, st);
-      }
-      ProfScope ps(c, st, "conv15_b");
-      eCRF_conv(c, EPI_HGRU_B, b, (int)n, st);
-    }
-    store_step(so, c->O.f(), c->I.f(), 0, (int)n, H, W, t, bf16_maps(c), st, is_fft(c->dtype) && fft_c4_maps(),
-               is_fft(c->dtype) && fft_c4_state());
+  const bool stagger = pre && multi && bb_stagger();   // slice k's backbone after slice k - 1's
+  if (stagger && !c->ev_pre) hip_check(hipEventCreateWithFlags(&c->ev_pre, hipEventDisableTiming), "hipEventCreate");
+  for (int k = 0; k < (int)slices.size(); ++k) {
+    const Slice& sl = slices[k];
+    if (k > 0) hip_check(hipStreamWaitEvent(sl.s, c->ev_fork, 0), "hipStreamWaitEvent");
+    if (stagger && k > 0) hip_check(hipStreamWaitEvent(sl.s, c->ev_pre, 0), "hipStreamWaitEvent");
+    if (pre) (*pre)(sl.b0, sl.cnt, sl.s);
+    if (stagger && k + 1 < ns) hip_check(hipEventRecord(c->ev_pre, sl.s), "hipEventRecord");
+    if (!multi) gate_init();   // one stream: after the backbone
+    circuit_range(c, sl.b0, sl.cnt, (int)n, H, W, T, o0_nhwc, final_dst2, so, sp, sl.s);
+    if (post) (*post)(sl.b0, sl.cnt, sl.s);
   }
-  if (post) (*post)(0, (int)n, st);
+  for (int k = 1; k < (int)slices.size(); ++k) {
+    hip_check(hipEventRecord(c->ev_join[k - 1], slices[k].s), "hipEventRecord");
+    hip_check(hipStreamWaitEvent(st, c->ev_join[k - 1], 0), "hipStreamWaitEvent");
+  }
 }
 
-// the initial output state for hidden_init (hgru_module.py:875-892) as an NHWC fp32 pointer:
-// MP_HIDDEN_GIVEN -> the caller's o0; ZEROS -> a zeroed workspace map; IDENTITY -> X (the
-// caller's NHWC x for the circuit, the C8 drive converted into a workspace map for the pose model)
-const float* hidden_state(mp_ctx* c, int hidden_init, const float* o0, const float* x_nhwc, int64_t n, int H, int W,
-                          hipStream_t st, uint64_t rng_seed = 0, int k = 64) {
+// an initial state (O0, or the general loops' I0) for hidden_init (hgru_module.py:875-892) as an NHWC fp32
+// pointer: MP_HIDDEN_GIVEN -> the caller's `given`; ZEROS -> buf, zeroed; RANDOM -> buf, drawn from
+// rng_seed; IDENTITY -> X (the caller's NHWC x for the circuit, the C8 drive converted into buf for the
+// pose model)
+const float* hidden_state(mp_ctx* c, DevBuf& buf, int hidden_init, const float* given, const float* x_nhwc, int64_t n,
+                          int H, int W, hipStream_t st, uint64_t rng_seed = 0, int k = 64) {
   const size_t bytes = (size_t)n * H * W * k * sizeof(float);
   switch (hidden_init) {
     case MP_HIDDEN_RANDOM:
       // a fresh xavier-uniform draw on the device (hgru_module.py:884-887), limit sqrt(6 / (k + k))
-      c->h0.alloc(bytes);
-      hip_check(launch_hidden_uniform(c->h0.f(), (int64_t)n * H * W * k, rng_seed, std::sqrt(6.0 / (2 * k)), st),
+      buf.alloc(bytes);
+      hip_check(launch_hidden_uniform(buf.f(), (int64_t)n * H * W * k, rng_seed, std::sqrt(6.0 / (2 * k)), st),
                 "hidden_init random");
-      return c->h0.f();
+      return buf.f();
     case MP_HIDDEN_GIVEN:
-      if (!o0) fail(MP_ERR_ARG, "o0 is NULL (hidden_init = MP_HIDDEN_GIVEN)");
-      return o0;
+      if (!given) fail(MP_ERR_ARG, "o0 is NULL (hidden_init = MP_HIDDEN_GIVEN)");
+      return given;
     case MP_HIDDEN_ZEROS:
-      c->h0.alloc(bytes);
-      hip_check(hipMemsetAsync(c->h0.p, 0, bytes, st), "hidden_init zeros");
-      return c->h0.f();
+      buf.alloc(bytes);
+      hip_check(hipMemsetAsync(buf.p, 0, bytes, st), "hidden_init zeros");
+      return buf.f();
     case MP_HIDDEN_IDENTITY:
       if (x_nhwc) return x_nhwc;
-      c->h0.alloc(bytes);
-      hip_check(launch_c8_to_nhwc(c->X.f(), c->h0.f(), (int)n, H, W, st, bf16_maps(c), 0, x_c4(c)), "hidden_init identity");
-      return c->h0.f();
+      buf.alloc(bytes);
+      hip_check(launch_c8_to_nhwc(c->X.f(), buf.f(), (int)n, H, W, st, bf16_maps(c), 0, x_c4(c)), "hidden_init identity");
+      return buf.f();
     default:
       fail(MP_ERR_ARG, "hidden_init must be MP_HIDDEN_GIVEN, _ZEROS, _IDENTITY or _RANDOM");
   }
@@ -1317,8 +1263,7 @@ int pose_fwd(mp_ctx* ctx, const float* depth, int64_t n, int64_t h, int64_t w, c
       ProfScope ps(ctx, s, "backbone");
       float* bA = ctx->bufA.f() + b0 * px;
       float* bB = ctx->bufB.f() + b0 * px;
-      float* xm = bf16_maps(ctx) ? reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(ctx->X.p) + b0 * px)
-                                 : ctx->X.f() + b0 * px;
+      float* xm = map_at(ctx->X, b0 * px, bf16_maps(ctx));
       hip_check(launch_conv1_pool_bn(depth + (size_t)b0 * h * w, ctx->conv1_w.f(), ctx->conv1_b.f(), ctx->bn0_s.f(),
                                      ctx->bn0_t.f(), bA, cnt, (int)h, (int)w, s),
                 "conv_1");
@@ -1357,11 +1302,9 @@ int pose_fwd(mp_ctx* ctx, const float* depth, int64_t n, int64_t h, int64_t w, c
     if (tp.pool1) hip_check(launch_c8_to_nhwc(ctx->bufA.f(), tp.pool1, N, H, W, st), "pool1 tap");
     if (tp.conv2) hip_check(launch_c8_to_nhwc(ctx->bufB.f(), tp.conv2, N, H, W, st), "conv2 tap");
     if (tp.conv3) hip_check(launch_c8_to_nhwc(ctx->X.f(), tp.conv3, N, H, W, st, bf16_maps(ctx), 0, x_c4(ctx)), "conv3 tap");
-    const float* h0 = hidden_state(ctx, fo.hidden_init, o0, nullptr, n, H, W, st, fo.rng_seed);
+    const float* h0 = hidden_state(ctx, ctx->h0, fo.hidden_init, o0, nullptr, n, H, W, st, fo.rng_seed);
     StateOut so;
-    so.O = fo.states_O;
-    so.I = fo.states_I;
-    so.T = ctx->timesteps;
+    const StateOut* sop = state_out(so, fo.states_O, fo.states_I, ctx->timesteps);
     // FFT dtypes: the last B epilogue writes fc_1's f16 hi / lo activation planes into fcin (same
     // bytes as the fp32 map), so fc_1 stages them by LDS-DMA with no conversion (bit-identical); the
     // hgru tap needs the fp32 map, and MP_FC_PRESPLIT=0 restores that form for A/B
@@ -1372,23 +1315,33 @@ int pose_fwd(mp_ctx* ctx, const float* depth, int64_t n, int64_t h, int64_t w, c
       sp.hi = reinterpret_cast<_Float16*>(ctx->fcin.p);
       sp.lo = fc_np == 3 ? sp.hi + (size_t)N * ctx->fc1_in : nullptr;
     }
-    // the head of rows b0 .. b0 + cnt on stream s: fc_1 on the split planes (partials in the slice's own
-    // S x cnt x Npad region of part, so slices run at once), relu + BN_4 into h1, fc_out (part2), its
-    // reduce into out.  Each row's sums are the same MFMA chains whatever the rows' count (the split
-    // count and slice length are functions of K and N only): bit-identical to the whole-batch head
+    // the head of rows b0 .. b0 + cnt on stream s: fc_1 in the context's form (exact fp32, f16x3 on the fp32
+    // map, or f16x3 on the split planes; partials in the rows' own S x cnt x Npad region of part, so slices
+    // run at once), relu + BN_4 into h1, fc_out (part2), its reduce into out.  Each row's sums are the same
+    // MFMA chains whatever the rows' count (the split count and slice length are functions of K and N
+    // only): a slice's head is bit-identical to its rows of the whole-batch head
     int ks1, ks2;
     const int S1 = fc_choose_splits(N, ctx->fc1_in, ctx->fc1_out, &ks1);
     const int S2 = fc_choose_splits(N, ctx->fc1_out, ctx->nout, &ks2);
     const size_t np1 = (size_t)(ctx->fc1_out + 31) / 32 * 32, np2 = (size_t)(ctx->nout + 31) / 32 * 32;
     const SliceFn head = [&](int b0, int cnt, hipStream_t s) {
-      float* h1 = ctx->h1.f() + (size_t)b0 * ctx->fc1_out;
+      const size_t r1 = (size_t)b0 * ctx->fc1_in, r2 = (size_t)b0 * ctx->fc1_out;   // the rows' offsets
+      float* h1 = ctx->h1.f() + r2;
       {
         ProfScope ps(ctx, s, "fc1");
         float* p1 = ctx->part.f() + (size_t)S1 * b0 * np1;
-        hip_check(launch_fc_gemm_x3p(sp.hi + (size_t)b0 * ctx->fc1_in, sp.lo ? sp.lo + (size_t)b0 * ctx->fc1_in : nullptr,
-                                     ctx->fc1_in, ctx->fc1_pk.p, ctx->fc1_unscale, p1, cnt, ctx->fc1_in, ctx->fc1_out,
-                                     S1, ks1, s, fc_np),
+        hip_check(ctx->dtype == MP_DTYPE_F32
+                      ? launch_fc_gemm(ctx->fcin.f() + r1, ctx->fc1_in, ctx->fc1_pk.v4(), p1, cnt, ctx->fc1_in,
+                                       ctx->fc1_out, S1, ks1, s)
+                  : presplit ? launch_fc_gemm_x3p(sp.hi + r1, sp.lo ? sp.lo + r1 : nullptr, ctx->fc1_in, ctx->fc1_pk.p,
+                                                  ctx->fc1_unscale, p1, cnt, ctx->fc1_in, ctx->fc1_out, S1, ks1, s, fc_np)
+                             : launch_fc_gemm_x3(ctx->fcin.f() + r1, ctx->fc1_in, ctx->fc1_pk.p, ctx->fc1_unscale, p1, cnt,
+                                                 ctx->fc1_in, ctx->fc1_out, S1, ks1, s, fc_np),
                   "fc_1 gemm");
+        if (tp.fc1)   // fc_1 + bias before the relu (same partial sums)
+          hip_check(launch_fc_reduce(p1, S1, cnt, ctx->fc1_out, ctx->fc1_b.f(), 0, nullptr, nullptr, tp.fc1 + r2,
+                                     ctx->fc1_out, s),
+                    "fc1 tap");
         hip_check(launch_fc_reduce(p1, S1, cnt, ctx->fc1_out, ctx->fc1_b.f(), 1, ctx->bn4_s.f(), ctx->bn4_t.f(), h1,
                                    ctx->fc1_out, s),
                   "fc_1 reduce");
@@ -1401,47 +1354,16 @@ int pose_fwd(mp_ctx* ctx, const float* depth, int64_t n, int64_t h, int64_t w, c
                                  ctx->nout, s),
                 "fc_out reduce");
     };
+    // per hGRU slice on its stream (MP_FC_SLICE), or once for the whole batch after the join: the taps'
+    // copies sit around that one call
     const bool head_slices = presplit && fc_slice() && !tp.fc1 && !tp.relu1;
-    run_circuit(ctx, n, H, W, ctx->timesteps, h0, ctx->fcin.f(), (so.O || so.I) ? &so : nullptr, st,
-                presplit ? &sp : nullptr, bb_pipe ? &backbone : nullptr, head_slices ? &head : nullptr);
-    if (head_slices) return;
+    run_circuit(ctx, n, H, W, ctx->timesteps, h0, ctx->fcin.f(), sop, st, presplit ? &sp : nullptr,
+                bb_pipe ? &backbone : nullptr, head_slices ? &head : nullptr);
     if (tp.hgru)
       hip_check(hipMemcpyAsync(tp.hgru, ctx->fcin.f(), (size_t)N * ctx->fc1_in * sizeof(float),
                                hipMemcpyDeviceToDevice, st),
                 "hgru tap");
-    {
-      ProfScope ps(ctx, st, "fc1");
-      int ks;
-      const int S = fc_choose_splits(N, ctx->fc1_in, ctx->fc1_out, &ks);
-      (void)S1;
-      (void)S2;
-      hip_check(ctx->dtype == MP_DTYPE_F32
-                    ? launch_fc_gemm(ctx->fcin.f(), ctx->fc1_in, ctx->fc1_pk.v4(), ctx->part.f(), N, ctx->fc1_in,
-                                     ctx->fc1_out, S, ks, st)
-                : presplit ? launch_fc_gemm_x3p(sp.hi, sp.lo, ctx->fc1_in, ctx->fc1_pk.p, ctx->fc1_unscale,
-                                                ctx->part.f(), N, ctx->fc1_in, ctx->fc1_out, S, ks, st, fc_np)
-                           : launch_fc_gemm_x3(ctx->fcin.f(), ctx->fc1_in, ctx->fc1_pk.p, ctx->fc1_unscale,
-                                               ctx->part.f(), N, ctx->fc1_in, ctx->fc1_out, S, ks, st, fc_np),
-                "fc_1 gemm");
-      if (tp.fc1)   // fc_1 + bias before the relu (same partial sums)
-        hip_check(launch_fc_reduce(ctx->part.f(), S, N, ctx->fc1_out, ctx->fc1_b.f(), 0, nullptr, nullptr, tp.fc1,
-                                   ctx->fc1_out, st),
-                  "fc1 tap");
-      hip_check(launch_fc_reduce(ctx->part.f(), S, N, ctx->fc1_out, ctx->fc1_b.f(), 1, ctx->bn4_s.f(),
-                                 ctx->bn4_t.f(), ctx->h1.f(), ctx->fc1_out, st),
-                "fc_1 reduce");
-    }
-    {
-      ProfScope ps(ctx, st, "fc_out");
-      int ks;
-      const int S2 = fc_choose_splits(N, ctx->fc1_out, ctx->nout, &ks);
-      hip_check(launch_fc_gemm(ctx->h1.f(), ctx->fc1_out, ctx->fco_pk.v4(), ctx->part.f(), N, ctx->fc1_out,
-                               ctx->nout, S2, ks, st),
-                "fc_out gemm");
-      hip_check(launch_fc_reduce(ctx->part.f(), S2, N, ctx->nout, ctx->fco_b.f(), 0, nullptr, nullptr, out,
-                                 ctx->nout, st),
-                "fc_out reduce");
-    }
+    if (!head_slices) head(0, N, st);
     if (tp.relu1)
       hip_check(hipMemcpyAsync(tp.relu1, ctx->h1.f(), (size_t)N * ctx->fc1_out * sizeof(float),
                                hipMemcpyDeviceToDevice, st),
@@ -1495,24 +1417,19 @@ int mp_hgru_circuit_fwd_opts(mp_ctx* ctx, const float* x, const float* o0, int64
   return guard([&] {
     const FwdOpts fo = read_opts(opts, false);
     const int hidden_init = fo.hidden_init;
-    float* states_O = fo.states_O;
-    float* states_I = fo.states_I;
     if (!ctx || !x || !o_out || (!o0 && hidden_init == MP_HIDDEN_GIVEN))
       fail(MP_ERR_ARG, "mp_hgru_circuit_fwd: null pointer");
     if (!ctx->finalized) fail(MP_ERR_STATE, "weights not finalized");
     if (ctx->has_var)
       fail(MP_ERR_STATE, "context finalized for a circuit variant: use mp_hgru_circuit_fwd_var");
+    StateOut so;
+    const StateOut* sop = state_out(so, fo.states_O, fo.states_I, timesteps);
     if (ctx->nhwc) {   // the channel-general loop runs the pose aux as its variant
       cn_check(ctx, n, h, w, k, timesteps);
       hip_check(hipSetDevice(ctx->device), "hipSetDevice");
       hipStream_t st = static_cast<hipStream_t>(stream);
-      const float* h0 = hidden_state(ctx, hidden_init, o0, x, n, (int)h, (int)w, st, fo.rng_seed, (int)k);
-      StateOut so;
-      so.O = states_O;
-      so.I = states_I;
-      so.T = timesteps;
-      nhwc_circuit(ctx, (int)n, (int)h, (int)w, timesteps, x, h0, nullptr, o_out, nullptr,
-                   (states_O || states_I) ? &so : nullptr, st);
+      const float* h0 = hidden_state(ctx, ctx->h0, hidden_init, o0, x, n, (int)h, (int)w, st, fo.rng_seed, (int)k);
+      nhwc_circuit(ctx, (int)n, (int)h, (int)w, timesteps, x, h0, nullptr, o_out, nullptr, sop, st);
       return;
     }
     if (k != 64) fail(MP_ERR_SHAPE, "channel count k must be 64");
@@ -1521,19 +1438,13 @@ int mp_hgru_circuit_fwd_opts(mp_ctx* ctx, const float* x, const float* o0, int64
     if (timesteps < 1 || timesteps > (int)ctx->rho.size())
       fail(MP_ERR_ARG, "timesteps must be in [1, len(rho)]");
     hip_check(hipSetDevice(ctx->device), "hipSetDevice");
+    if (ctx->model == MP_MODEL_HGRU_POSE)   // its output affine is BN_3, fused into the loop's last kernel
+      fail(MP_ERR_UNSUPPORTED, "use an MP_MODEL_HGRU_CIRCUIT context for the standalone circuit");
     hipStream_t st = static_cast<hipStream_t>(stream);
     ensure_ws(ctx, n, h, w);
     hip_check(launch_nhwc_to_c8(x, ctx->X.f(), (int)n, (int)h, (int)w, st, bf16_maps(ctx), x_c4(ctx)), "nhwc_to_c8");
-    if (ctx->model == MP_MODEL_HGRU_POSE) {
-      // the pose context's output affine is BN_3: use identity by running with a temporary copy
-      fail(MP_ERR_UNSUPPORTED, "use an MP_MODEL_HGRU_CIRCUIT context for the standalone circuit");
-    }
-    const float* h0 = hidden_state(ctx, hidden_init, o0, x, n, (int)h, (int)w, st, fo.rng_seed);
-    StateOut so;
-    so.O = states_O;
-    so.I = states_I;
-    so.T = timesteps;
-    run_circuit(ctx, n, (int)h, (int)w, timesteps, h0, o_out, (states_O || states_I) ? &so : nullptr, st);
+    const float* h0 = hidden_state(ctx, ctx->h0, hidden_init, o0, x, n, (int)h, (int)w, st, fo.rng_seed);
+    run_circuit(ctx, n, (int)h, (int)w, timesteps, h0, o_out, sop, st);
   });
 }
 
@@ -1603,31 +1514,13 @@ int mp_hgru_circuit_fwd_var(mp_ctx* ctx, const float* x, const float* o0, const 
       ensure_ws(ctx, n, h, w);
       hip_check(launch_nhwc_to_c8(x, ctx->X.f(), (int)n, (int)h, (int)w, st), "nhwc_to_c8");
     }
-    const float* h0 = hidden_state(ctx, hidden_init, o0, x, n, (int)h, (int)w, st, m.rng_seed + m.rng_call, (int)k);
-    const float* hi = nullptr;
-    if (live_i) {   // the initial I, made like O0 (hgru_module.py:875-892)
-      const size_t bytes = (size_t)n * h * w * k * sizeof(float);
-      switch (hidden_init) {
-        case MP_HIDDEN_GIVEN: hi = i0; break;
-        case MP_HIDDEN_IDENTITY: hi = x; break;
-        case MP_HIDDEN_ZEROS:
-          ctx->i0.alloc(bytes);
-          hip_check(hipMemsetAsync(ctx->i0.p, 0, bytes, st), "hidden_init zeros (I)");
-          hi = ctx->i0.f();
-          break;
-        default:   // MP_HIDDEN_RANDOM (hidden_state checked the value): a second, independent draw
-          ctx->i0.alloc(bytes);
-          hip_check(launch_hidden_uniform(ctx->i0.f(), n * h * w * k, m.rng_seed_i + m.rng_call,
-                                          std::sqrt(6.0 / (2 * k)), st),
-                    "hidden_init random (I)");
-          hi = ctx->i0.f();
-      }
-    }
+    const float* h0 = hidden_state(ctx, ctx->h0, hidden_init, o0, x, n, (int)h, (int)w, st, m.rng_seed + m.rng_call, (int)k);
+    // the initial I, made like O0 (hgru_module.py:875-892); MP_HIDDEN_RANDOM: a second, independent draw
+    const float* hi = live_i ? hidden_state(ctx, ctx->i0, hidden_init, i0, x, n, (int)h, (int)w, st,
+                                            m.rng_seed_i + m.rng_call, (int)k)
+                             : nullptr;
     StateOut so;
-    so.O = states_O;
-    so.I = states_I;
-    so.T = timesteps;
-    const StateOut* sop = (states_O || states_I) ? &so : nullptr;
+    const StateOut* sop = state_out(so, states_O, states_I, timesteps);
     if (cn)
       nhwc_circuit(ctx, (int)n, (int)h, (int)w, timesteps, x, h0, hi, o_out, i_out, sop, st);
     else

@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstdlib>
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -15,6 +17,13 @@ namespace mp {
 
 constexpr int C = 64;      // channels of every hGRU / backbone map (hgru_pose.py:50-81)
 constexpr int NQ = C / 8;  // channel chunks in the C8 layout
+
+// an integer MP_* switch of the environment: atoi of the variable, dflt when it is unset.  Each getter
+// keeps the value in a static const of its own, so a variable is read once per process
+inline int env_int(const char* name, int dflt) {
+  const char* e = std::getenv(name);
+  return e ? std::atoi(e) : dflt;
+}
 
 __device__ __forceinline__ size_t c8_index(int b, int q, int y, int x, int e, int H, int W) {
   return ((((size_t)b * NQ + q) * H + y) * W + x) * 8 + e;

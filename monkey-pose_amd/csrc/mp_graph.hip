@@ -100,11 +100,6 @@ struct GraphState {
 namespace mpr {
 namespace {
 
-int env_int(const char* k, int dflt) {
-  const char* v = std::getenv(k);
-  return v && *v ? std::atoi(v) : dflt;
-}
-
 bool dbg() {
   static const int v = env_int("MP_GRAPH_DEBUG", 0);
   return v != 0;

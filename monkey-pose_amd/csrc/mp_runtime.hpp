@@ -144,9 +144,9 @@ struct mp_ctx {
   // ---- workspace ----
   int64_t cap_batch = 0;
   int64_t cap_hw = 0;
-  DevBuf bufA, bufB, X, O, I, Og, fcin, part, part2, h1;   // part2: fc_out's partials (per-slice heads)
-  DevBuf h0;                // hidden_init zeros / identity: the NHWC initial state (allocated on use)
-  DevBuf i0;                // general loop, MP_HIDDEN_RANDOM: the NHWC draw of the initial I
+  DevBuf bufA, bufB, X, O, I, Og, fcin, part, part2, h1;   // part / part2: fc_1's / fc_out's split-K partials
+  DevBuf h0;                // hidden_init zeros / identity / random: the NHWC initial state O0 (allocated on use)
+  DevBuf i0;                // general loops: the initial I made the same way (hidden_state)
   DevBuf specS, specY, specP;   // MP_DTYPE_F32_FFT: input / output spectra, spatial conv result
 
   // ---- dense / hierarchical regressors (mp_regressors.hip) ----

@@ -32,9 +32,9 @@ import hgru_variants_ref as V  # noqa: E402
 from helpers import BF16_REL_TOL, BF16_STATE_REL_TOL, FP32_REL_TOL, HGRU_POSE_AUX, MG, pkg  # noqa: E402
 
 # the loops of mp_abi.hip, by the name the table gives them
-FUSED = "fused"          # fft4_circuit_range: the four-step loop (k_fft4.hip), fp32_fft and bf16
-DIRECT = "direct"        # run_circuit's direct-conv loop (k_conv64.hip, k_conv64x3.hip)
-SIX = "six"              # MP_FFT4=0: fft_step (one stream) / fft_circuit_range (two), k_fft.hip
+FUSED = "fused"          # circuit_range's four-step loop (k_fft4.hip), fp32_fft and bf16
+DIRECT = "direct"        # circuit_range's direct-conv loop (k_conv64.hip, k_conv64x3.hip)
+SIX = "six"              # MP_FFT4=0: circuit_range's six-launch loop (k_fft.hip), on one stream or two
 GENERAL = "general"      # var_circuit, k_circuit_var.hip
 NHWC = "nhwc"            # nhwc_circuit, k_circuit_nhwc.hip
 POSE = "pose"            # the pose model: backbone, the fused loop at len(rho) steps, the head

@@ -334,7 +334,7 @@ def test_o0_direct_switch_at_one_step(children):
 
 @pytest.mark.parametrize("dtype", ["fp32_fft", "bf16"])
 def test_six_launch_loop_at_one_step(children, dtype):
-    """MP_FFT4=0 at T = 1: fft_step on one stream (n = 2) and fft_circuit_range on two (n = 66), whose
+    """MP_FFT4=0 at T = 1: the six-launch loop on one stream (n = 2) and on two (n = 66), whose
     `t == T - 1 -> final_out` (mode 1: the NHWC result) is then also their first step.  The call's own
     output -- at n = 66 also the images at the slice edges -- and the stored states against the oracle;
     stack[:, 0] is the output (bf16: to the rounding of the bf16 state map)"""
