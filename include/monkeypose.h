@@ -23,6 +23,15 @@
  *     "cnn/fc_1/fc_1_weights"); a leading "cnn/" scope is optional.  The library copies them.
  *   - Calls on one context are serialised by the caller and are asynchronous on `stream`
  *     (a hipStream_t; NULL = default stream).  One context per device.
+ *     Asynchronous means ordered: every function with a `stream` argument reads its device inputs after
+ *     the work queued on `stream` before the call, and what it writes is complete for work queued on
+ *     `stream` after it, also where the call fans out over private streams (the hGRU batch slices, the
+ *     layer graph): those wait for an event of `stream` and `stream` waits for theirs.  No such function
+ *     waits on the host, except that the first call of a context at a new batch or map shape may
+ *     (workspace growth, a new graph plan, stream creation).  A context moves to another stream only
+ *     behind an event recorded after its last call; different contexts share no device state.  Host
+ *     arguments (cam, com_scale, thresholds, bones, style) are read before the call returns.
+ *     (tests/stream_order_cases.py classifies every such function; INTEGRATION.md "Streams".)
  *   - Status: MP_OK (0) or a negative MP_ERR_*; mp_last_error() gives a thread-local message.
  *     No C++ exception crosses the ABI.  Shapes are validated on the host before any launch.
  */
