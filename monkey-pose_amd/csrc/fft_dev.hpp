@@ -120,35 +120,30 @@ __device__ __forceinline__ cpx swp(cpx a) {
 #ifndef FFT_EPI_EARLY
 #define FFT_EPI_EARLY 1     // chunk 0's X / O loads issued before the inverse row phase (implies the pipelining)
 #endif
-// FFT_C4: the loop's P2 and I maps in the C4 layout (mp_common.hpp c4_index; bit 0: P2, bit 1: I), so
-// the inverse kernels (fft_inv, inv_a_fwd, their latency forms) write each block's 4-channel group as
-// one contiguous run instead of 16-B halves of 32-B C8 pixels; spec_epi_b and the state stacks read
-// them there.  Probes of the two writes made contiguous: fft_inv 0.134 -> 0.125 ms, inv_a_fwd 0.340 ->
-// 0.328 ms at B = 256.  Unswizzled C4 reads cost fp32 epi_b 0.259 -> 0.289 ms on one box; with the
-// odd group's row halves swapped (C4_SWZ) the same-box A/B against C8 is fp32 10.65 -> 10.46 ms, bf16
-// 6.20 -> 6.10, B = 64 3.34 -> 3.28 (profiles/r4o).  Bit 2 puts the state O there too (gate_init /
-// epi_b write it, inv_a_fwd's A epilogue and epi_b read it): fp32 10.21-10.27 -> 10.03-10.04 ms
-// (epi_b 0.279 -> 0.256, inv_a_fwd 0.314 -> 0.309), bf16 6.13-6.15 -> 6.11 (profiles/r4o/c4_state_ab.log).
-// Bit 3 the drive X (conv_3's backbone epilogue writes it, ConvArgs::dst_c4): fp32 9.95 -> 9.89 ms
+// The loop's P2, I, O and X maps are in the C4 layout (mp_common.hpp c4_index), so the inverse kernels
+// (fft_inv, inv_a_fwd, their latency forms) write each block's 4-channel group as one contiguous run
+// instead of 16-B halves of 32-B C8 pixels; spec_epi_b and the state stacks read them there.  Probes
+// of the P2 and I writes made contiguous: fft_inv 0.134 -> 0.125 ms, inv_a_fwd 0.340 -> 0.328 ms at
+// B = 256.  Unswizzled C4 reads cost fp32 epi_b 0.259 -> 0.289 ms on one box; with the odd group's row
+// halves swapped (C4_SWZ) the same-box A/B against C8 is fp32 10.65 -> 10.46 ms, bf16 6.20 -> 6.10,
+// B = 64 3.34 -> 3.28 (profiles/r4o).  The state O there too (gate_init / epi_b write it, inv_a_fwd's
+// A epilogue and epi_b read it): fp32 10.21-10.27 -> 10.03-10.04 ms (epi_b 0.279 -> 0.256, inv_a_fwd
+// 0.314 -> 0.309), bf16 6.13-6.15 -> 6.11 (profiles/r4o/c4_state_ab.log).  The drive X (conv_3's
+// backbone epilogue writes it, ConvArgs::dst_c4; the A epilogue reads it): fp32 9.95 -> 9.89 ms
 // (inv_a_fwd 0.307 -> 0.299), bf16 6.08-6.10 -> 6.05-6.06 (profiles/r4o/c4_drive_ab.log).  Og (read by
-// the forward FFT's row loads, where the C4 probe gained nothing) stays C8.  0 restores C8 maps.
-#ifndef FFT_C4
-#define FFT_C4 15
-#endif
-// (bit 0: P2, bit 1: I)
-__device__ __forceinline__ size_t pp_index(int b, int q, int y, int x, int e, int H, int W) {
-  return (FFT_C4 & 1) ? c4_index(b, q, y, x, e, H, W) : c8_index(b, q, y, x, e, H, W);
+// the forward FFT's row loads, where the C4 probe gained nothing) stays C8.
+// Element index in each of the four maps, named for the map at the call site:
+__device__ __forceinline__ size_t pp_index(int b, int q, int y, int x, int e, int H, int W) {   // P2
+  return c4_index(b, q, y, x, e, H, W);
 }
-__device__ __forceinline__ size_t ii_index(int b, int q, int y, int x, int e, int H, int W) {
-  return (FFT_C4 & 2) ? c4_index(b, q, y, x, e, H, W) : c8_index(b, q, y, x, e, H, W);
+__device__ __forceinline__ size_t ii_index(int b, int q, int y, int x, int e, int H, int W) {   // I
+  return c4_index(b, q, y, x, e, H, W);
 }
-// bit 3: the drive X (written by conv_3's backbone epilogue, ConvArgs::dst_c4; read by the A epilogue)
-__device__ __forceinline__ size_t xx_index(int b, int q, int y, int x, int e, int H, int W) {
-  return (FFT_C4 & 8) ? c4_index(b, q, y, x, e, H, W) : c8_index(b, q, y, x, e, H, W);
+__device__ __forceinline__ size_t xx_index(int b, int q, int y, int x, int e, int H, int W) {   // the drive X
+  return c4_index(b, q, y, x, e, H, W);
 }
-// bit 2: the state O (written by gate_init / epi_b, read by inv_a_fwd's A epilogue and epi_b)
-__device__ __forceinline__ size_t oo_index(int b, int q, int y, int x, int e, int H, int W) {
-  return (FFT_C4 & 4) ? c4_index(b, q, y, x, e, H, W) : c8_index(b, q, y, x, e, H, W);
+__device__ __forceinline__ size_t oo_index(int b, int q, int y, int x, int e, int H, int W) {   // the state O
+  return c4_index(b, q, y, x, e, H, W);
 }
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
@@ -323,9 +318,6 @@ __device__ __forceinline__ void dft9(cpx (&x)[9]) {
 // transform than Cooley-Tukey n = 9 n1 + n2; both index maps are register renamings)
 template <int S>
 __device__ __forceinline__ void fft72(cpx (&v)[72]) {
-#ifdef FFT_PROBE_NOFFT   // timing probe (tools/fft_stamps.hip): data movement without the transforms
-  return;
-#endif
   cpx a[9][8];
 #pragma unroll
   for (int n2 = 0; n2 < 9; ++n2) {

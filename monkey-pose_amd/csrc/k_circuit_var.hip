@@ -7,7 +7,7 @@
 // of lane (h, x) = channel 32n + 8(r>>2) + 4h + (r&3) of pixel x), so the gate products run on the
 // MFMA gate fragments (gate() below) with no lane movement and every map access is a 16-byte load
 // or store per lane, one pass over each map.  The state maps X, O, I and the conv inputs are C8; P
-// is C8 from the direct convs and the FFT path's P layout (fft_dev.hpp pp_index) from
+// is C8 from the direct convs and the FFT path's P layout (C4: fft_dev.hpp pp_index) from
 // launch_fft_inv.  The variant is wave-uniform: its branches are scalar.
 #include "circuit_var.hpp"
 #include "fft_dev.hpp"
@@ -205,9 +205,8 @@ static hipError_t launch_cv(int half, const CvArgs& a, int B, hipStream_t st) {
   if (a.p_fft && !c4_width_ok(a.W)) return hipErrorInvalidValue;
   const long nseg = (long)B * a.H * (a.W / 32);
   if (nseg > (1L << 30)) return hipErrorInvalidValue;
-  // the FFT path hands P over in its own layout (C4 when FFT_C4 bit 0 is set, else C8)
-  constexpr bool fft_p_c4 = (FFT_C4 & 1) != 0;
-  return a.p_fft && fft_p_c4 ? launch_nl<true>(half, a, (int)nseg, st) : launch_nl<false>(half, a, (int)nseg, st);
+  // the FFT path hands P over as a C4 map
+  return a.p_fft ? launch_nl<true>(half, a, (int)nseg, st) : launch_nl<false>(half, a, (int)nseg, st);
 }
 
 hipError_t launch_circuit_in(const CvArgs& a, int B, hipStream_t st) {

@@ -13,7 +13,6 @@
 #include "mp_kernels.hpp"
 
 #include <algorithm>
-#include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <utility>
@@ -769,18 +768,17 @@ int fc_choose_splits(int M, int K, int N, int* kslice) {
   // blocks = one full round of 3 blocks on each of the 256 CUs (64 slices left a 1/3-full second
   // round); and at least 384 blocks per 128-row tile whatever N is (the dense head's fc_1_1 / fc_1_2,
   // N = 512: 18 / 12 slices gave 192 / 128 blocks at batch 256 and 0.25 ms each).  A function of
-  // K and N only, so a crop's sums group the same way at every batch.  MP_FC_KSLICE (A/B only)
-  // fixes the slice length.
-  static const int kfix = env_int("MP_FC_KSLICE", INT_MIN);   // INT_MIN: unset (no atoi result)
-  static const bool kenv = kfix != INT_MIN;
-  static const int ksz = kenv ? std::max(32, kfix) : 5440;
+  // K and N only, so a crop's sums group the same way at every batch.
   const int nt = ((N + 31) / 32 + 3) / 4;   // 128-column tiles
-  static const int smallk = std::max(32, env_int("MP_FC_SMALLK", 128));   // K per slice below 32k (A/B knob)
-  int S = K >= 32768 ? std::max(1, K / ksz) : std::min(64, (K + smallk - 1) / smallk);
-  if (K >= 32768 && !kenv) S = std::min(std::max(S, (384 + nt - 1) / nt), K / 512);
-  // N a multiple of 256 (fc_1: 1,024): the 256 x 256 tiles of launch_fc_gemm_x3p's 256-row kernel,
-  // 256 / (N / 256) K slices (64 for fc_1: one block on each of the 256 CUs at batch 256)
-  if (K >= 32768 && !kenv && FC_P_BIG && N % 256 == 0) S = std::min(std::max(1, 256 / (N / 256)), K / 512);
+  int S;
+  if (K >= 32768) {
+    S = std::min(std::max(std::max(1, K / 5440), (384 + nt - 1) / nt), K / 512);
+    // N a multiple of 256 (fc_1: 1,024): the 256 x 256 tiles of launch_fc_gemm_x3p's 256-row kernel,
+    // 256 / (N / 256) K slices (64 for fc_1: one block on each of the 256 CUs at batch 256)
+    if (FC_P_BIG && N % 256 == 0) S = std::min(std::max(1, 256 / (N / 256)), K / 512);
+  } else {
+    S = std::min(64, (K + 127) / 128);
+  }
   if (S < 1) S = 1;
   int ks = (K + S - 1) / S;
   const int q = K % 64 == 0 ? 64 : FC_BK;   // whole 64-deep steps where K allows (the one-product kernel)

@@ -208,15 +208,9 @@ __device__ __forceinline__ void inv_cols_to_T(const void* __restrict__ Y, int b,
 #pragma unroll
       for (int fy = 0; fy < 72; ++fy) v[fy] = unpack_bf2(src[fy * FS]);
     } else {
-#ifdef FFT_PROBE_YCOAL   // timing probe (tools/bench_fft.hip): the block's Y run read wave-contiguously
-      const cpx* src = static_cast<const cpx*>(Y) + ((size_t)b * 16 + cq) * NF * 4 + tid;
-#pragma unroll
-      for (int fy = 0; fy < 72; ++fy) v[fy] = src[fy * FX * 4];
-#else
       const cpx* src = static_cast<const cpx*>(Y) + off;
 #pragma unroll
       for (int fy = 0; fy < 72; ++fy) v[fy] = src[fy * FS];
-#endif
     }
     fft72<1>(v);
 #pragma unroll
@@ -249,13 +243,7 @@ constexpr int RLD = 73;
 // (separate L2s), so blocks i and i+8 share an XCD: giving them the two halves of a chunk lets one
 // L2 fetch (or write back) each line once instead of two XCDs each moving the whole line
 // (rocprofv3 FETCH/WRITE_SIZE showed 2x the algorithmic bytes on these maps otherwise).
-__device__ __forceinline__ int fft_block_img(int blk) {
-#ifdef FFT_PROBE_WRAP   // timing probe (tools/fft_stamps.hip): every block works on one of WRAP images
-  return (blk >> 4) % FFT_PROBE_WRAP;
-#else
-  return blk >> 4;
-#endif
-}
+__device__ __forceinline__ int fft_block_img(int blk) { return blk >> 4; }
 __device__ __forceinline__ int fft_block_cq(int blk) {
   const int p = blk & 15;
   return 2 * (p & 7) + (p >> 3);
@@ -404,13 +392,8 @@ __global__ __launch_bounds__(FNT, 3) void fft_fwd3_kernel(const float* __restric
   cpx v[72];
   const int y = tid >> 1, p = tid & 1;
   if (tid < 128) {
-#ifdef FFT_PROBE_OGC4   // timing probe (tools/bench_fft.hip): the map read as a C4 group (16-B pixels)
-    const size_t row = ((size_t)(b * 16 + cq) * H + (y < H ? y : 0)) * W * 4;
-    constexpr int PXS = 4;
-#else
     const size_t row = c8_index(b, q, y < H ? y : 0, 0, e0, H, W);
     constexpr int PXS = 8;
-#endif
 #pragma unroll
     for (int k = 0; k < 32; ++k) {
       const int x = 2 * k + p;
@@ -461,11 +444,7 @@ __global__ __launch_bounds__(FNT, BF ? FFT_MINB_BF : FFT_MINB) void fft_inv_kern
   for (int i = tid; i < H * W; i += FNT) {
     const int yy = i / W, x = i - yy * W;
     const cpx a = T.get((2 * yy) * RLD + x), c = T.get((2 * yy + 1) * RLD + x);
-#ifdef FFT_PROBE_PCOAL   // timing probe (tools/bench_fft.hip): the block's P quarter written contiguously
-    map_st4_stream<BM>(P, ((size_t)b * 16 + cq) * 4096 * 4 + 4 * i, f32x4{a.x, a.y, c.x, c.y});
-#else
     map_st4_stream<BM>(P, pp_index(b, q, yy, x, e0, H, W), f32x4{a.x, a.y, c.x, c.y});
-#endif
   }
   FFT_STAMP_AT(5);
 }
@@ -495,13 +474,8 @@ __global__ __launch_bounds__(FNT, BF ? FFT_MINB_BF : FFT_MINB) void fft_inv_a_fw
     for (int u = 0; u < EU; ++u) {
       const int i = min(k * ECH + u * FNT + tid, 64 * 64 - 1);
       const int yy = min(i >> 6, H - 1), x = min(i & 63, W - 1);
-#ifdef FFT_PROBE_XOC4   // timing probe (tools/bench_fft.hip): X / O read as C4 groups
-      const size_t idx = c4_index(b, q, yy, x, e0, H, W);
-#else
-      const size_t idx = c8_index(b, q, yy, x, e0, H, W);
-#endif
-      xs[u] = map_ld4<BM>(p.X, (FFT_C4 & 8) ? xx_index(b, q, yy, x, e0, H, W) : idx);
-      os[u] = map_ld4<BM>(p.O, (FFT_C4 & 4) ? oo_index(b, q, yy, x, e0, H, W) : idx);
+      xs[u] = map_ld4<BM>(p.X, xx_index(b, q, yy, x, e0, H, W));
+      os[u] = map_ld4<BM>(p.O, oo_index(b, q, yy, x, e0, H, W));
     }
   };
   inv_cols_to_T<BF>(Y, b, cq, tid, T);
@@ -555,17 +529,9 @@ __global__ __launch_bounds__(FNT, BF ? FFT_MINB_BF : FFT_MINB) void fft_inv_a_fw
           f32x4 iv;
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-#ifdef FFT_PROBE_NOTANH   // timing probe: the A epilogue without tanhf
-            iv[j] = xv[cur][u][j] - (be[j] * ov[cur][u][j] + nu[j]) * (pv[j] + lat[j]);
-#else
             iv[j] = atanh_f(epi_a(xv[cur][u][j], ov[cur][u][j], pv[j], be[j], nu[j], lat[j]));
-#endif
           }
-#ifdef FFT_PROBE_ICOAL   // timing probe (tools/bench_fft.hip): the block's I quarter written contiguously
-          map_st4_stream<BM>(p.dst, ((size_t)b * 16 + cq) * 4096 * 4 + 4 * i, iv);
-#else
           map_st4_stream<BM>(p.dst, ii_index(b, q, yy, x, e0, H, W), iv);
-#endif
           T.set(ia, {iv[0], iv[1]});
           T.set(ic, {iv[2], iv[3]});
         } else {
@@ -905,7 +871,7 @@ static int lfft_maxb() {
 // weights are fetched from HBM once.
 constexpr int SG_NI = 32;              // images per block
 #ifndef SPEC_SMALLB
-#define SPEC_SMALLB 8   // batches up to this run spec_gemm_kernel<0, 8> (8-image tiles); 0 = off
+#define SPEC_SMALLB 8   // batches up to this run spec_gemm_kernel<8> (8-image tiles); 0 = off
 #endif
 #ifndef SPEC_SMALL_HALF
 #define SPEC_SMALL_HALF 1   // 8-image kernel: the weights in two halves of 4 k-steps (64 VGPRs instead of 128):
@@ -923,8 +889,7 @@ constexpr int SG_SLD = 33;             // S tile pitch (16-B units) per (cq, par
 constexpr int SG_YLD = 16 * 4 * 2 + 1; // Y tile pitch (16-B units) per image
 // NI: images per block -- 32, or 8 for batches <= SPEC_SMALLB (a quarter of the S tile's loads and
 // LDS; the MFMA columns of images past NI are zero, the per-output product order is the same)
-template <int PROBE = 0, int NI = SG_NI>   // timing probes (tools/bench_fft.hip): 1 = no MFMA, 2 = no S / weight loads,
-                                          // 3 = no weight loads, 4 = no S loads
+template <int NI = SG_NI>
 __global__ __launch_bounds__(256, NI == SG_NI ? 2 : SPEC_SMALL_MINB) void spec_gemm_kernel(const uint4* __restrict__ S, const uint4* __restrict__ Gc,
                                                            uint4* __restrict__ Y, int B, int ngrp, float unscale) {
   constexpr int SLD = NI + 1;               // S tile pitch (16-B units) per (cq, part, f) row
@@ -946,7 +911,7 @@ __global__ __launch_bounds__(256, NI == SG_NI ? 2 : SPEC_SMALL_MINB) void spec_g
     const int idx = it * 256 + tid, line = idx >> 3, piece = idx & 7;
     const int bl = line >> 4, cq = line & 15;
     const int b = min(img0 + bl, B - 1);
-    pre[it] = S[(PROBE == 2 || PROBE == 4) ? (tid & 63) : (((size_t)b * 16 + cq) * NF + 4 * quad) * 2 + piece];
+    pre[it] = S[(((size_t)b * 16 + cq) * NF + 4 * quad) * 2 + piece];
   }
   // ---- weights of frequency f = 4 quad + wv: one f16x8 per (t, h, part, co block), all 32 issued
   // before the S tile is waited for, so their L2 latency overlaps the tile's HBM latency (the
@@ -954,7 +919,7 @@ __global__ __launch_bounds__(256, NI == SG_NI ? 2 : SPEC_SMALL_MINB) void spec_g
   // half's MFMAs; the per-output k-step order is unchanged) ----
   constexpr int TW = (NI != SG_NI && SPEC_SMALL_HALF) ? 4 : 8;   // k-steps per weight batch
   const int f = 4 * quad + wv;
-  const uint4* gw = Gc + ((PROBE == 2 || PROBE == 3) ? 0 : (size_t)f * 2 * 16 * 64);
+  const uint4* gw = Gc + (size_t)f * 2 * 16 * 64;
   uint4 wr[TW][2][2];
   auto load_w = [&](int t0) {
 #pragma unroll
@@ -993,16 +958,12 @@ __global__ __launch_bounds__(256, NI == SG_NI ? 2 : SPEC_SMALL_MINB) void spec_g
         const f16x8 ah0 = __builtin_bit_cast(f16x8, gh ^ m), al0 = __builtin_bit_cast(f16x8, gl ^ m);
         const f16x8 ah1 = __builtin_bit_cast(f16x8, (gh >> 16) | (gh << 16));
         const f16x8 al1 = __builtin_bit_cast(f16x8, (gl >> 16) | (gl << 16));
-        if constexpr (PROBE == 1) {   // keep the operand loads alive, skip the matrix cores
-          acc[cb][0] += (float)(sh[0] + sl[0] + ah0[0] + al0[0] + ah1[1] + al1[1]);
-        } else {
-          acc[cb] = mfma16(al0, sh, acc[cb]);
-          acc[cb] = mfma16(ah0, sl, acc[cb]);
-          acc[cb] = mfma16(ah0, sh, acc[cb]);
-          acc[2 + cb] = mfma16(al1, sh, acc[2 + cb]);
-          acc[2 + cb] = mfma16(ah1, sl, acc[2 + cb]);
-          acc[2 + cb] = mfma16(ah1, sh, acc[2 + cb]);
-        }
+        acc[cb] = mfma16(al0, sh, acc[cb]);
+        acc[cb] = mfma16(ah0, sl, acc[cb]);
+        acc[cb] = mfma16(ah0, sh, acc[cb]);
+        acc[2 + cb] = mfma16(al1, sh, acc[2 + cb]);
+        acc[2 + cb] = mfma16(ah1, sl, acc[2 + cb]);
+        acc[2 + cb] = mfma16(ah1, sh, acc[2 + cb]);
       }
     }
   }
@@ -1427,9 +1388,6 @@ __global__ void pack_gate_bf_kernel(const float* __restrict__ g, uint4* __restri
 }
 
 // ------------------------------------------------------------------------------------ launchers
-bool fft_c4_maps() { return (FFT_C4 & 2) != 0; }
-bool fft_c4_state() { return (FFT_C4 & 4) != 0; }
-bool fft_c4_drive() { return (FFT_C4 & 8) != 0; }
 bool fft_bf16_maps() {
   static const bool v = env_int("MP_BF16_MAPS", 1) != 0;
   return v;
@@ -1515,7 +1473,7 @@ hipError_t launch_fft_inv_a_fwd(const void* Y, const ConvArgs& a, void* S, int B
   return hipGetLastError();
 }
 
-// batches up to SPEC_SMALLB run the spectral GEMM on 8-image tiles (spec_gemm_kernel<0, 8>, ceil(B / 8)
+// batches up to SPEC_SMALLB run the spectral GEMM on 8-image tiles (spec_gemm_kernel<8>, ceil(B / 8)
 // image groups; bit-identical to the 32-image tiles, which measured slower there)
 static int spec_smallb() { return SPEC_SMALLB; }
 
@@ -1526,10 +1484,10 @@ hipError_t launch_spec_gemm(const void* S, const void* Gx, void* Y, int B, float
     hipLaunchKernelGGL(spec_gemm_bf_kernel, dim3(NQ16 * 16 * ngrp), dim3(256), 0, st, static_cast<const uint4*>(S),
                        static_cast<const uint4*>(Gx), static_cast<uint4*>(Y), B, ngrp);
   else if (small)
-    hipLaunchKernelGGL((spec_gemm_kernel<0, 8>), dim3(NQ8 * 8 * ngrp), dim3(256), 0, st, static_cast<const uint4*>(S),
+    hipLaunchKernelGGL((spec_gemm_kernel<8>), dim3(NQ8 * 8 * ngrp), dim3(256), 0, st, static_cast<const uint4*>(S),
                        static_cast<const uint4*>(Gx), static_cast<uint4*>(Y), B, ngrp, unscale);
   else
-    hipLaunchKernelGGL(spec_gemm_kernel<0>, dim3(NQ8 * 8 * ngrp), dim3(256), 0, st, static_cast<const uint4*>(S),
+    hipLaunchKernelGGL(spec_gemm_kernel<>, dim3(NQ8 * 8 * ngrp), dim3(256), 0, st, static_cast<const uint4*>(S),
                        static_cast<const uint4*>(Gx), static_cast<uint4*>(Y), B, ngrp, unscale);
   return hipGetLastError();
 }

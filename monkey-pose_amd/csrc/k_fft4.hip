@@ -31,18 +31,14 @@ constexpr int RK_ITEMS = FX * 64;                    // (fx, channel) columns of
 constexpr int RK_T = 8 * FX * 64;                    // T[n1][fx][c] complex: 151,552 B of LDS
 constexpr int RK_SP = 68;                            // staging pitch (floats) per pixel (16-B fragment reads)
 
-// complex index of channel 0 of Z[b][fx][k1][n2] (ZLAYOUT 1, the default: a column block's 8 row
-// classes of one image are one contiguous 4-KB run; interleaved same-box A/B 8.21 -> 8.15 ms per fp32
-// forward, bf16 unchanged, profiles/r5_ab/r5s2) or of Z[b][n2][fx][k1] (ZLAYOUT 0: a row block's
-// (b, n2) slice contiguous)
-#ifndef ZLAYOUT
-#define ZLAYOUT 1
-#endif
+// complex index of channel 0 of Z[b][fx][k1][n2]: a column block's 8 row classes of one image are one
+// contiguous 4-KB run (col8p_kernel's DMA relies on it).  Against Z[b][n2][fx][k1] (a row block's
+// (b, n2) slice contiguous), interleaved same-box A/B: 8.21 -> 8.15 ms per fp32 forward, bf16
+// unchanged (profiles/r5_ab/r5s2)
 __device__ __forceinline__ size_t z_off(int b, int n2, int fx, int k1) {
-  if constexpr (ZLAYOUT == 1) return ((((size_t)b * FX + fx) * 9 + k1) * 8 + n2) * 64;
-  return ((((size_t)b * 8 + n2) * FX + fx) * 9 + k1) * 64;
+  return ((((size_t)b * FX + fx) * 9 + k1) * 8 + n2) * 64;
 }
-constexpr int Z_K1 = ZLAYOUT == 1 ? 8 * 64 : 64;   // complex stride between consecutive k1
+constexpr int Z_K1 = 8 * 64;   // complex stride between consecutive k1
 
 enum { ROW_A = 0, ROW_B = 1, ROW_FINAL = 2, ROW_INIT = 3 };
 
@@ -424,12 +420,6 @@ constexpr int R8_GATE = 2 * 4 * 2 * 64;                  // f16x8 of one gate's 
 constexpr int R8_T = (8 * 64 * RK_SP * 4 + R8_GATE * 16) / 8;   // 155,648 B: T grown by 512 B for FINAL
 static_assert(R8_T >= RK_T && (8 * 32 * RK_SP * 4 + 2 * R8_GATE * 16) <= R8_T * 8, "staging + gate weights fit");
 
-#ifndef R8_INIT_MNT   // (A/B) row(INIT) follows the maps' policy too
-#define R8_INIT_MNT 0
-#endif
-#ifndef R8_SEGPF
-#define R8_SEGPF 0
-#endif
 // BF: MP_DTYPE_BF16 -- Z and the hGRU maps in bf16, the gates one bf16 product (gate_bf); transforms,
 // epilogue math and the NHWC output fp32
 // ZNT: Z read and written non-temporal (MP_ROW8_ZNT); MNT: the fp32 maps (X, O, I, O0) too (MP_MAP_NT)
@@ -452,9 +442,7 @@ __global__ __launch_bounds__(R8_NT, 1) void row8_kernel(void* __restrict__ Z, Co
   constexpr bool OR = MODE == ROW_B || MODE == ROW_FINAL, IR = MODE == ROW_B || MODE == ROW_INIT;
   constexpr int GN = BF ? R8_GATE / 2 : R8_GATE;   // uint4 per gate (bf16: one product, no lo plane)
   float P[64];
-  constexpr bool SEGPF = R8_SEGPF && (MODE == ROW_A || MODE == ROW_B);
-  constexpr bool MNTM = MNT && (R8_INIT_MNT || MODE != ROW_INIT);   // this mode's map policy
-  SegIn L0;
+  constexpr bool MNTM = MNT && MODE != ROW_INIT;   // this mode's map policy (row(INIT): the default one)
   if constexpr (MODE != ROW_INIT) {
     {
       cpx u[R8_NIT][9];
@@ -477,12 +465,9 @@ __global__ __launch_bounds__(R8_NT, 1) void row8_kernel(void* __restrict__ Z, Co
       }
     }
     lds_barrier();
-    // R8_SEGPF (A/B, default 0): the first epilogue segment's maps requested here, during the inverse
-    // row transforms instead of in front of the segment.  Same box, B = 256: row A 0.272 ms either
-    // way, row B 0.297 -> 0.312 (profiles/r6/ab/ab_row.jsonl): not kept
-    if constexpr (SEGPF) {
-      if (live) rk_load_seg<MODE, BF, MNTM>(p, O0, b, y, 0, lane, L0);
-    }
+    // Measured and removed: the first epilogue segment's maps requested here, during the inverse row
+    // transforms instead of in front of the segment.  Same box, B = 256: row A 0.272 ms either way,
+    // row B 0.297 -> 0.312 (profiles/r6/ab/ab_row.jsonl)
     {
       cpx A[FX];
 #pragma unroll
@@ -521,8 +506,7 @@ __global__ __launch_bounds__(R8_NT, 1) void row8_kernel(void* __restrict__ Z, Co
       const int xs = 32 * sg;
       if (xs >= W) continue;   // wave-uniform
       SegIn L;
-      if (SEGPF && sg == 0) L = L0;
-      else rk_load_seg<MODE, BF, MNTM>(p, O0, b, y, xs, lane, L);
+      rk_load_seg<MODE, BF, MNTM>(p, O0, b, y, xs, lane, L);
       if constexpr (MODE != ROW_INIT) {
 #pragma unroll
         for (int q = 0; q < 32; ++q) stg[q * RK_SP + lane] = P[xs + q];
@@ -691,20 +675,16 @@ constexpr int CG_YLD = 16 * 4 * 2 + 1;               // Y tile pitch (16-B units
 static_assert(CG_NI * CG_YLD <= CG_HALF, "a half's Y tile fits the S tile half it replaces");
 constexpr int CG_NC8 = (Z_CLS + 7) / 8;              // 42 groups of 8 classes (one per XCD)
 
-// CG_SWZ (default 1): rows of 16 units with image column bl ^ cq, so that a DFT thread group's S
-// writes (eight channel groups cq of one image at a 2,176-B stride: 4-way bank conflicts on the padded
-// rows) and the GEMM's fragment reads (16 images of a row, or two rows' halves) both spread over the 64
-// banks; and the Y tile's frequency slot rotated by the channel group, (q + cq) & 7, so the inverse
-// DFT's reads (one frequency of 16 channel groups, a 256-B stride: 8-way) do too.  Placement only: the
-// values and their arithmetic are unchanged.
-#ifndef CG_SWZ
-#define CG_SWZ 1
-#endif
+// The S tile's rows are 16 units with image column bl ^ cq, so that a DFT thread group's S writes
+// (eight channel groups cq of one image: 4-way bank conflicts on rows of pitch CG_SLD at a 2,176-B
+// stride, the form this replaced) and the GEMM's fragment reads (16 images of a row, or two rows'
+// halves) both spread over the 64 banks; and the Y tile's frequency slot rotated by the channel
+// group, (q + cq) & 7, so the inverse DFT's reads (one frequency of 16 channel groups, a 256-B stride:
+// 8-way) do too.  Placement only: the values and their arithmetic are unchanged.
 __device__ __forceinline__ int cg_s(int k2, int cq, int part, int bl) {   // S tile index (16-B units)
-  if constexpr (CG_SWZ) return (k2 >> 2) * CG_HALF + ((cq * 2 + part) * 4 + (k2 & 3)) * 16 + (bl ^ cq);
-  return (k2 >> 2) * CG_HALF + ((cq * 2 + part) * 4 + (k2 & 3)) * CG_SLD + bl;
+  return (k2 >> 2) * CG_HALF + ((cq * 2 + part) * 4 + (k2 & 3)) * 16 + (bl ^ cq);
 }
-__device__ __forceinline__ int cg_yq(int q, int cq) { return CG_SWZ ? (q + cq) & 7 : q; }   // Y tile slot
+__device__ __forceinline__ int cg_yq(int q, int cq) { return (q + cq) & 7; }   // Y tile slot
 __device__ __forceinline__ f32x4 mfma16x16(f16x8 a, f16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }
@@ -750,50 +730,10 @@ __device__ __forceinline__ void cg_forward(const f32x4 (&zin)[8], int k1, uint4*
 // (gr, gi) pairs as stored; the S fragment supplies the two forms, (sr, -si) for the real rows
 // (gr sr - gi si) and (si, sr) for the imaginary rows (gr si + gi sr): a sign flip and a half swap per S
 // dword (16 VALU per k-step) instead of four weight forms (64).  w[mq][0 | 1] = the hi | lo planes.
-template <bool LEAN = false>
 __device__ __forceinline__ void cg_kstep(const uint4* tile, int k2, int t, int kq, int jj, const uint4 (&w)[4][2],
                                          f32x4 (&acc)[8]) {
   const uint4 m = {0x80000000u, 0x80000000u, 0x80000000u, 0x80000000u};
   const uint4 uh = tile[cg_s(k2, 4 * t + kq, 0, jj)], ul = tile[cg_s(k2, 4 * t + kq, 1, jj)];
-  if constexpr (LEAN) {   // the real rows' MFMAs, then the imaginary rows' (fewer S forms live at once)
-    const f16x8 sh = __builtin_bit_cast(f16x8, uh ^ m), sl = __builtin_bit_cast(f16x8, ul ^ m);
-#pragma unroll
-    for (int mq = 0; mq < 4; ++mq) {
-      const f16x8 ah = __builtin_bit_cast(f16x8, w[mq][0]), al = __builtin_bit_cast(f16x8, w[mq][1]);
-      acc[mq] = mfma16x16(al, sh, acc[mq]);
-      acc[mq] = mfma16x16(ah, sl, acc[mq]);
-      acc[mq] = mfma16x16(ah, sh, acc[mq]);
-    }
-    const f16x8 sh2 = __builtin_bit_cast(f16x8, (uh >> 16) | (uh << 16));
-    const f16x8 sl2 = __builtin_bit_cast(f16x8, (ul >> 16) | (ul << 16));
-#pragma unroll
-    for (int mq = 0; mq < 4; ++mq) {
-      const f16x8 ah = __builtin_bit_cast(f16x8, w[mq][0]), al = __builtin_bit_cast(f16x8, w[mq][1]);
-      acc[4 + mq] = mfma16x16(al, sh2, acc[4 + mq]);
-      acc[4 + mq] = mfma16x16(ah, sl2, acc[4 + mq]);
-      acc[4 + mq] = mfma16x16(ah, sh2, acc[4 + mq]);
-    }
-    return;
-  }
-  const f16x8 sh = __builtin_bit_cast(f16x8, uh ^ m), sl = __builtin_bit_cast(f16x8, ul ^ m);
-  const f16x8 sh2 = __builtin_bit_cast(f16x8, (uh >> 16) | (uh << 16));
-  const f16x8 sl2 = __builtin_bit_cast(f16x8, (ul >> 16) | (ul << 16));
-#pragma unroll
-  for (int mq = 0; mq < 4; ++mq) {
-    const f16x8 ah = __builtin_bit_cast(f16x8, w[mq][0]), al = __builtin_bit_cast(f16x8, w[mq][1]);
-    acc[mq] = mfma16x16(al, sh, acc[mq]);
-    acc[mq] = mfma16x16(ah, sl, acc[mq]);
-    acc[mq] = mfma16x16(ah, sh, acc[mq]);
-    acc[4 + mq] = mfma16x16(al, sh2, acc[4 + mq]);
-    acc[4 + mq] = mfma16x16(ah, sl2, acc[4 + mq]);
-    acc[4 + mq] = mfma16x16(ah, sh2, acc[4 + mq]);
-  }
-}
-
-// cg_kstep on S fragments already read (uh / ul: the hi / lo fragment of k-step t): the same MFMAs in
-// the same order as cg_kstep
-__device__ __forceinline__ void cg_kstep_frag(uint4 uh, uint4 ul, const uint4 (&w)[4][2], f32x4 (&acc)[8]) {
-  const uint4 m = {0x80000000u, 0x80000000u, 0x80000000u, 0x80000000u};
   const f16x8 sh = __builtin_bit_cast(f16x8, uh ^ m), sl = __builtin_bit_cast(f16x8, ul ^ m);
   const f16x8 sh2 = __builtin_bit_cast(f16x8, (uh >> 16) | (uh << 16));
   const f16x8 sl2 = __builtin_bit_cast(f16x8, (ul >> 16) | (ul << 16));
@@ -810,24 +750,14 @@ __device__ __forceinline__ void cg_kstep_frag(uint4 uh, uint4 ul, const uint4 (&
 }
 
 // weights of k-step t for wave k2 of class cls (both planes, the wave's four row blocks)
-// CG_WNT (A/B, default 0): the weight loads non-temporal
-#ifndef CG_WNT
-#define CG_WNT 0
-#endif
+// (loaded non-temporal they made the column kernel slower: DESIGN.md 8)
 __device__ __forceinline__ void cg_wload(const uint4* __restrict__ Gc, int cls, int k2, int t, int kq, int jj,
                                          uint4 (&w)[4][2]) {
   const uint4* gw = Gc + (size_t)(cls * 8 + k2) * 2 * 16 * 64;
 #pragma unroll
   for (int mq = 0; mq < 4; ++mq) {
-#if CG_WNT
-    typedef unsigned u4v __attribute__((ext_vector_type(4)));
-    const u4v* gv = reinterpret_cast<const u4v*>(gw);
-    w[mq][0] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(gv + (0 * 16 + 4 * t + kq) * 64 + 16 * mq + jj));
-    w[mq][1] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(gv + (1 * 16 + 4 * t + kq) * 64 + 16 * mq + jj));
-#else
     w[mq][0] = gw[(0 * 16 + 4 * t + kq) * 64 + 16 * mq + jj];
     w[mq][1] = gw[(1 * 16 + 4 * t + kq) * 64 + 16 * mq + jj];
-#endif
   }
 }
 
@@ -947,12 +877,21 @@ __global__ __launch_bounds__(512, 2) void col8_kernel(cpx* __restrict__ Z, const
 // weights (its frequency's 4 k-steps, 128 VGPRs) stay in registers while the range stays in one class
 // (an item range spans at most two or three classes), so no vector-memory load is waited for between
 // the DMA's issue and its use: vmcnt counts loads, stores and LDS-DMA together in issue order, and a
-// wait for a younger load would drain the prefetch.  The item math is cg_forward / cg_kstep /
+// wait for a younger load would drain the prefetch.  The waits for an item's DMA are therefore counted
+// (wait_vm<N>: at most N younger operations still in flight) from the two per-item constants next to
+// the loops that issue them, ST stores and DMA pieces per wave.  The invariant: nothing else is counted
+// between an item's DMA and its use (the weight loads are waited for to zero where they are issued).
+// The item math is cg_forward / cg_kstep /
 // cg_ystore / cg_inverse, as in col8_kernel: bit-identical outputs.
 // ---------------------------------------------------------------------------------------------
 constexpr int CP_SLOT = 2 * CG_HALF;                 // uint4 per LDS slot (69,632 B)
 static_assert(CG_NI * 8 * 64 * 8 <= CP_SLOT * 16, "an item's raw partials fit a slot");
-static_assert(ZLAYOUT == 1, "col8p DMA: an image's 8 row classes are one contiguous 4-KiB run of Z");
+
+template <int N>
+__device__ __forceinline__ void wait_vm() {
+  static_assert(0 <= N && N <= 63, "vmcnt is a 6-bit count");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
 
 // one LDS-DMA wave instruction: 64 lanes x 16 B from each lane's gsrc to LDS bytes [lds, lds + 1024)
 // (M0 = the wave-uniform LDS base, written and restored in the same statement)
@@ -967,12 +906,13 @@ __device__ __forceinline__ void glds16(const void* gsrc, uint32_t lds) {
 // Measured and removed (same box, B = 256; profiles/r6/ab/ab_col8.jsonl): item it + 2's DMA issued
 // before item it's stores (0.186 vs 0.170 ms); an item's stores held in registers and issued before
 // the next item's GEMM (0.178 vs 0.169) or two after each of its k-steps (0.212); every k-step's S
-// fragments read before the first MFMA (0.1742 vs 0.1744).  Timing-only builds (tools/exp_lib.sh
-// -DCOL8P_NO...): no DMA wait 0.166 vs 0.171, no stores 0.147, no GEMM 0.129, no DMA and no stores
-// (the item arithmetic alone) 0.103 of which the GEMM phase is 0.053, every item on the first class's
-// weights 0.152 (the 85 MB of weights not read).  A class change's weights requested right after the
-// previous item's GEMM instead of behind a vmcnt(0) at the class's first item: 0.1687 vs 0.1676, not
-// kept (profiles/r6/ab/ab_col8_phases.jsonl).
+// fragments read before the first MFMA (0.1742 vs 0.1744); the loop software-pipelined so that item
+// k's GEMM ran beside item k - 1's inverse DFT and stores (0.179 vs 0.170).  Timing-only builds with a
+// phase left out (wrong values; removed): no DMA wait 0.166 vs 0.171, no stores 0.147, no GEMM 0.129,
+// no DMA and no stores (the item arithmetic alone) 0.103 of which the GEMM phase is 0.053, every item
+// on the first class's weights 0.152 (the 85 MB of weights not read).  A class change's weights
+// requested right after the previous item's GEMM instead of behind a vmcnt(0) at the class's first
+// item: 0.1687 vs 0.1676, not kept (profiles/r6/ab/ab_col8_phases.jsonl).
 template <bool ZNT>
 __global__ __launch_bounds__(512, 1) void col8p_kernel(cpx* __restrict__ Z, const uint4* __restrict__ Gc, int B,
                                                        int ngrp, int nitems, float unscale) {
@@ -987,15 +927,14 @@ __global__ __launch_bounds__(512, 1) void col8p_kernel(cpx* __restrict__ Z, cons
   const int bl = tid >> 5, a = tid & 31, cq = a >> 1, hf = a & 1;
   const int kq = lane >> 4, jj = lane & 15, k2 = wv;
   const uint32_t lds0 = (uint32_t)(uintptr_t)slots;
+  // what a wave issues per item, for the counted waits: ST stores of its results, DMA pieces of partials
+  constexpr int ST = 8, DMA = 8;
   // item it -> slot s: wave wv moves images 2 wv, 2 wv + 1 of the group (four 1-KiB quarters each)
   auto dma = [&](int it, int s) {
-#ifdef COL8P_NODMA   // timing only (with COL8P_NOWAIT): no partials loaded
-    if (it >= 0) return;
-#endif
     const int cls = it / ngrp, grp = it - cls * ngrp;
     const int fx = cls / 9, k1 = cls - fx * 9;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
+    for (int i = 0; i < DMA; ++i) {
       const int il = 2 * wv + (i >> 2);
       const int b = min(grp * CG_NI + il, B - 1);
       const char* src = reinterpret_cast<const char*>(Z + z_off(b, 0, fx, k1)) + (i & 3) * 1024 + lane * 16;
@@ -1019,18 +958,16 @@ __global__ __launch_bounds__(512, 1) void col8p_kernel(cpx* __restrict__ Z, cons
     uint4* tile = slots + s * CP_SLOT;
     const int cls = it / ngrp, grp = it - cls * ngrp;
     const int fx = cls / 9, k1 = cls - fx * 9;
-    // this item's DMA is older than: the previous item's 8 stores and the next item's 8 DMA pieces (a
+    // this item's DMA is older than: the previous item's stores and the next item's DMA pieces (a
     // class change's weight loads only make the wait longer)
     const bool nx = it + 1 < it1;
-#ifndef COL8P_NOWAIT   // (timing only when defined: no wait for the DMA, reads whatever has landed)
     if (it == it0) {
-      if (nx) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (nx) wait_vm<DMA>();
+      else wait_vm<0>();
     } else {
-      if (nx) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+      if (nx) wait_vm<ST + DMA>();
+      else wait_vm<ST>();
     }
-#endif
     lds_barrier();   // every wave's pieces have landed
     {
       f32x4 zin[8];
@@ -1038,11 +975,7 @@ __global__ __launch_bounds__(512, 1) void col8p_kernel(cpx* __restrict__ Z, cons
 #pragma unroll
       for (int n2 = 0; n2 < 8; ++n2) zin[n2] = raw[n2 * 32];
       lds_barrier();   // the raw partials are read: the slot becomes the S tile
-#ifndef COL8P_NODFT   // (timing-only A/B builds: tools/exp_lib.sh ... -DCOL8P_NODFT etc.)
       cg_forward(zin, k1, tile, cq, hf, bl);
-#else
-      if (zin[0][0] == 12345.f) tile[tid] = uint4{};
-#endif
     }
     if (cls != wcls) {   // block-uniform
       wcls = cls;
@@ -1052,166 +985,28 @@ __global__ __launch_bounds__(512, 1) void col8p_kernel(cpx* __restrict__ Z, cons
     }
     lds_barrier();
     f32x4 acc[8] = {};
-#ifndef COL8P_NOGEMM
 #pragma unroll
     for (int t = 0; t < 4; ++t) cg_kstep(tile, k2, t, kq, jj, w[t], acc);
-#endif
     lds_barrier();   // every wave has read the S tile
     cg_ystore(tile, k2, kq, jj, acc, unscale);
     lds_barrier();
     f32x4 out[8];
     cg_yread(tile, cq, hf, bl, out);
-#ifndef COL8P_NOINV
     cg_inverse_regs(out, k1, out);
-#endif
     // images past B (a partial last group) store image B - 1's values over it: the same bytes, since
-    // their DMA read image B - 1 too -- every item issues exactly 8 stores, as the counted waits assume
+    // their DMA read image B - 1 too -- every item issues exactly ST stores, as the counted waits assume
     const int b = min(grp * CG_NI + bl, B - 1);
     f32x4* zb = reinterpret_cast<f32x4*>(Z + z_off(b, 0, fx, k1)) + a;
-#ifndef COL8P_NOSTORE   // timing only: no stores
+    static_assert(ST == 8, "one store per row class n2");
 #pragma unroll
-    for (int n2 = 0; n2 < 8; ++n2) {
+    for (int n2 = 0; n2 < ST; ++n2) {
       f32x4* zp = zb + n2 * 32;   // z_off(b, n2, fx, k1) - z_off(b, 0, fx, k1) = 64 n2 complex = 32 n2 f32x4
       if constexpr (ZNT) __builtin_nontemporal_store(out[n2], zp);
       else *zp = out[n2];
     }
-#else
-    if (out[0][0] == 12345.f) zb[0] = out[0];
-#endif
     if (it + 2 < it1) {
       lds_barrier();   // every thread has read its Y values: the slot takes item it + 2
       dma(it + 2, s);
-    }
-  }
-}
-
-// col8q_kernel: col8p_kernel's blocks and LDS-DMA prefetch, software-pipelined so that the matrix
-// cores and the vector ALUs work at the same time: item k's GEMM (MFMA, weights in registers, S from
-// the working slot) runs beside item k - 1's inverse DFT and stores (VALU on the thread's 8 Y values,
-// read from the Y tile into registers at the end of item k - 1).  Per item:
-//   GEMM(k) || inverse(k - 1) + stores(k - 1);  Y(k) -> W;  yv <- W;
-//   wait DMA(k + 1) in P;  raw(k + 1) -> DFT -> S(k + 1) over it in P;  DMA(k + 2) -> W;  swap W, P.
-// Item k + 2's DMA is issued one item ahead of its use.  The same item arithmetic (cg_*): bit-identical.
-template <bool ZNT>
-__global__ __launch_bounds__(512, 1) void col8q_kernel(cpx* __restrict__ Z, const uint4* __restrict__ Gc, int B,
-                                                       int ngrp, int nitems, float unscale) {
-  __shared__ uint4 slots[2 * CP_SLOT];   // 139,264 B
-  const int nblk = gridDim.x, per = nblk / 8, r8 = nblk % 8, xg = blockIdx.x % 8, q = blockIdx.x / 8;
-  const int v = (xg < r8 ? xg * (per + 1) : r8 * (per + 1) + (xg - r8) * per) + q;
-  const int it0 = (int)((int64_t)v * nitems / nblk), it1 = (int)((int64_t)(v + 1) * nitems / nblk);
-  if (it0 >= it1) return;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int kq = lane >> 4, jj = lane & 15, k2 = wv;
-  const uint32_t lds0 = (uint32_t)(uintptr_t)slots;
-  auto dma = [&](int it, int s) {
-    const int cls = it / ngrp, grp = it - cls * ngrp;
-    const int fx = cls / 9, k1 = cls - fx * 9;
-    const int lq = opaque(lane);   // (not hoisted out of the item loop)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int il = 2 * wv + (i >> 2);
-      const int b = min(grp * CG_NI + il, B - 1);
-      const char* src = reinterpret_cast<const char*>(Z + z_off(b, 0, fx, k1)) + (i & 3) * 1024 + lq * 16;
-      const uint32_t dst = lds0 + (uint32_t)(s * CP_SLOT * 16 + il * 4096 + (i & 3) * 1024);
-      glds16(src, __builtin_amdgcn_readfirstlane(dst));
-    }
-  };
-  // raw partials of the item in slot s -> S tile over them (two barriers)
-  auto forward = [&](int it, int s) {
-    // thread indices re-derived from an opaque tid: their address math is not hoisted out of the loop
-    // (held live, or spilled, across the GEMM)
-    const int tq = opaque(tid), bl = tq >> 5, a = tq & 31, cq = a >> 1, hf = a & 1;
-    uint4* tile = slots + s * CP_SLOT;
-    const int cls = it / ngrp, k1 = cls % 9;
-    f32x4 zin[8];
-    const f32x4* raw = reinterpret_cast<const f32x4*>(tile) + bl * 256 + a;
-#pragma unroll
-    for (int n2 = 0; n2 < 8; ++n2) zin[n2] = raw[n2 * 32];
-    lds_barrier();   // the raw partials are read: the slot becomes the S tile
-    cg_forward(zin, k1, tile, cq, hf, bl);
-  };
-  constexpr unsigned VMCNT0 = 0x0F70;   // vmcnt(0) expcnt(7) lgkmcnt(15), seen by hipcc's bookkeeping
-  uint4 w[4][4][2];
-  int wcls = it0 / ngrp;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) cg_wload(Gc, wcls, k2, t, kq, jj, w[t]);
-  __builtin_amdgcn_s_waitcnt(VMCNT0);
-  dma(it0, 0);
-  if (it0 + 1 < it1) {
-    dma(it0 + 1, 1);
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  lds_barrier();
-  forward(it0, 0);
-  lds_barrier();
-  f32x4 yv[8];   // the previous item's Y values of this thread's channels
-  // one item; WI: with the previous item's inverse DFT and stores beside the GEMM (every item but the
-  // first: a branch there would put them in a block of their own, after the MFMAs)
-  auto item = [&](int it, auto WI) {
-    const int s = (it - it0) & 1;
-    uint4* tile = slots + s * CP_SLOT;
-    const int cls = it / ngrp;
-    if (cls != wcls) {   // block-uniform: before this item's GEMM
-      wcls = cls;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) cg_wload(Gc, wcls, k2, t, kq, jj, w[t]);
-      __builtin_amdgcn_s_waitcnt(VMCNT0);
-    }
-    f32x4 acc[8] = {};
-#pragma unroll
-    for (int t = 0; t < 4; ++t) cg_kstep<true>(tile, k2, t, kq, jj, w[t], acc);
-    if constexpr (decltype(WI)::value) {
-      const int pit = it - 1, pcls = pit / ngrp, pgrp = pit - pcls * ngrp;
-      const int pfx = pcls / 9, pk1 = pcls - pfx * 9;
-      f32x4 out[8];
-      cg_inverse_regs(yv, pk1, out);
-      const int tq = opaque(tid);
-      const int b = min(pgrp * CG_NI + (tq >> 5), B - 1);   // (images past B: image B - 1's bytes again)
-#pragma unroll
-      for (int n2 = 0; n2 < 8; ++n2) {
-        f32x4* zp = reinterpret_cast<f32x4*>(Z + z_off(b, n2, pfx, pk1)) + (tq & 31);
-        if constexpr (ZNT) __builtin_nontemporal_store(out[n2], zp);
-        else *zp = out[n2];
-      }
-    }
-    lds_barrier();   // every wave has read the S tile
-    {
-      const int lq = opaque(lane);
-      cg_ystore(tile, k2, lq >> 4, lq & 15, acc, unscale);
-    }
-    if (it + 1 < it1) {
-      // item it + 1's DMA (issued one item ago) is older than this item's 8 stores only
-      if constexpr (decltype(WI)::value) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      lds_barrier();   // every wave's pieces have landed; the Y tile is complete
-      forward(it + 1, s ^ 1);
-      {
-        const int tq = opaque(tid);   // after the forward DFT: fewer registers live beside it
-        cg_yread(tile, (tq & 31) >> 1, tq & 1, tq >> 5, yv);
-      }
-      lds_barrier();   // the S tile of item it + 1 is complete; every thread has read its Y values
-      if (it + 2 < it1) dma(it + 2, s);
-    } else {
-      lds_barrier();
-      const int tq = opaque(tid);
-      cg_yread(tile, (tq & 31) >> 1, tq & 1, tq >> 5, yv);
-    }
-  };
-  item(it0, std::false_type{});
-  for (int it = it0 + 1; it < it1; ++it) item(it, std::true_type{});
-  {   // the last item's inverse DFT and stores
-    const int pit = it1 - 1, pcls = pit / ngrp, pgrp = pit - pcls * ngrp;
-    const int pfx = pcls / 9, pk1 = pcls - pfx * 9;
-    f32x4 out[8];
-    cg_inverse_regs(yv, pk1, out);
-    const int b = min(pgrp * CG_NI + (tid >> 5), B - 1);
-#pragma unroll
-    for (int n2 = 0; n2 < 8; ++n2) {
-      f32x4* zp = reinterpret_cast<f32x4*>(Z + z_off(b, n2, pfx, pk1)) + (tid & 31);
-      if constexpr (ZNT) __builtin_nontemporal_store(out[n2], zp);
-      else *zp = out[n2];
     }
   }
 }
@@ -1221,10 +1016,9 @@ __global__ __launch_bounds__(512, 1) void col8q_kernel(cpx* __restrict__ Z, cons
 // v_mfma_f32_16x16x32_bf16 product per (k-step, row block, re|im) against the class-major bf16
 // weights Gb[f][cq][co] (16 KiB per frequency), fp32 accumulation, DFTs and twiddles in fp32.
 constexpr int CB_HALF = 16 * 4 * CG_SLD;             // one frequency half of the bf16 S tile (16-B units)
-// (CG_SWZ: rows of 16 units, image column img ^ c, as cg_s)
+// (rows of 16 units, image column img ^ c, as cg_s)
 __device__ __forceinline__ int cb_s(int k2, int c, int img) {
-  if constexpr (CG_SWZ) return (k2 >> 2) * CB_HALF + (c * 4 + (k2 & 3)) * 16 + (img ^ c);
-  return (k2 >> 2) * CB_HALF + (c * 4 + (k2 & 3)) * CG_SLD + img;
+  return (k2 >> 2) * CB_HALF + (c * 4 + (k2 & 3)) * 16 + (img ^ c);
 }
 // the bf16 item phases, shared by col8_bf_kernel and col8p_bf_kernel (bit-identical): the thread's 8
 // bf16 row-class partials (channels 2a, 2a + 1) -> twiddle, 8-point DFT -> bf16 S tile
@@ -1327,12 +1121,13 @@ __global__ __launch_bounds__(512, 1) void col8p_bf_kernel(void* __restrict__ Zv,
   const int bl = tid >> 5, a = tid & 31, cq = a >> 1, hf = a & 1;
   const int kq = lane >> 4, jj = lane & 15, k2 = wv;
   const uint32_t lds0 = (uint32_t)(uintptr_t)slots;
+  constexpr int ST = 8, DMA = 4;   // stores and DMA pieces a wave issues per item (the counted waits)
   // item it -> slot s: wave wv moves images 2 wv, 2 wv + 1 (2 KiB each, two 1-KiB pieces)
   auto dma = [&](int it, int s) {
     const int cls = it / ngrp, grp = it - cls * ngrp;
     const int fx = cls / 9, k1 = cls - fx * 9;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < DMA; ++i) {
       const int il = 2 * wv + (i >> 1);
       const int b = min(grp * CG_NI + il, B - 1);
       const char* src = reinterpret_cast<const char*>(Z + z_off(b, 0, fx, k1)) + (i & 1) * 1024 + lane * 16;
@@ -1353,14 +1148,14 @@ __global__ __launch_bounds__(512, 1) void col8p_bf_kernel(void* __restrict__ Zv,
     uint4* tile = slots + s * CP_SLOT;
     const int cls = it / ngrp, grp = it - cls * ngrp;
     const int fx = cls / 9, k1 = cls - fx * 9;
-    // this item's DMA is older than the previous item's 8 stores and the next item's 4 DMA pieces
+    // this item's DMA is older than the previous item's stores and the next item's DMA pieces
     const bool nx = it + 1 < it1;
     if (it == it0) {
-      if (nx) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (nx) wait_vm<DMA>();
+      else wait_vm<0>();
     } else {
-      if (nx) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+      if (nx) wait_vm<ST + DMA>();
+      else wait_vm<ST>();
     }
     lds_barrier();   // every wave's pieces have landed
     {
@@ -1386,10 +1181,11 @@ __global__ __launch_bounds__(512, 1) void col8p_bf_kernel(void* __restrict__ Zv,
     lds_barrier();
     f32x4 yo[8];
     cg_inverse(tile, k1, cq, hf, bl, yo);
-    // images past B: image B - 1's bytes again; exactly 8 stores per item, as the counted waits assume
+    // images past B: image B - 1's bytes again; exactly ST stores per item, as the counted waits assume
     const int b = min(grp * CG_NI + bl, B - 1);
+    static_assert(ST == 8, "one store per row class n2");
 #pragma unroll
-    for (int n2 = 0; n2 < 8; ++n2) {
+    for (int n2 = 0; n2 < ST; ++n2) {
       u2v_t* zp = reinterpret_cast<u2v_t*>(Z + z_off(b, n2, fx, k1)) + a;
       if constexpr (ZNT) __builtin_nontemporal_store(cb_pack(yo[n2]), zp);
       else *zp = cb_pack(yo[n2]);
@@ -1410,20 +1206,15 @@ bool fft4_enabled() {
 // MP_MAP_NT: row8_kernel / rowq_a_kernel's map loads and stores (X, O, I; fp32 or bf16) non-temporal (1)
 // or default policy (0).  Default: on for forwards of >= 128 images, whose maps are far larger than the
 // 256 MB Infinity Cache: they then stop evicting the two convolutions' spectral weights (fp32 2 x 87 MB,
-// bf16 2 x 44 MB, read by every column launch) from it; row(INIT) keeps the default policy
-// (R8_INIT_MNT).  Same box, bit-identical (profiles/r6/ab/ab_map_nt.jsonl): fp32 B = 256 7.92 -> 7.70 ms
+// bf16 2 x 44 MB, read by every column launch) from it; row(INIT) keeps the default policy.
+// Same box, bit-identical (profiles/r6/ab/ab_map_nt.jsonl): fp32 B = 256 7.92 -> 7.70 ms
 // per forward (col8p 0.166 -> 0.151, row A 0.273 -> 0.266, row B 0.307 -> 0.304), B = 128 4.10 -> 4.05;
 // bf16 B = 256 4.98 -> 4.72, B = 128 2.555 -> 2.518.  Not below 128: fp32 B = 64 (slices of 32) 2.364 ->
 // 2.398, B = 32 1.40 -> 1.43; bf16 B = 64 1.495 -> 1.505
-#ifndef MAP_NT_MINB
-#define MAP_NT_MINB 128
-#endif
-#ifndef MAP_NT_MINB_BF
-#define MAP_NT_MINB_BF 128
-#endif
+constexpr int MAP_NT_FROM = 128;   // images per forward, fp32 and bf16
 static bool map_nt(bool bf, int ntot) {
   static const int v = env_int("MP_MAP_NT", -1);
-  return v < 0 ? ntot >= (bf ? MAP_NT_MINB_BF : MAP_NT_MINB) : v != 0;
+  return v < 0 ? ntot >= MAP_NT_FROM : v != 0;
 }
 
 // MP_COL8_ZNT: the column kernels' Z loads and stores non-temporal (1) or default policy (0).  Default:
@@ -1441,23 +1232,12 @@ static bool col8_znt(bool bf, int B, int ntot) {
   return v < 0 ? !bf && !z_default_policy(bf, B, ntot) : v != 0;
 }
 
-// MP_COL8P: slices of at least this many images run col8p_kernel (fp32; 0 = never); MP_COL8P_BLOCKS:
-// its grid (default: one block per CU).  Same box (profiles/r6/ab/ab_col8_batches.jsonl): B = 256 (two
+// MP_COL8P: slices of at least this many images run col8p_kernel / col8p_bf_kernel (0 = never), on a
+// grid of one block per CU.  Same box (profiles/r6/ab/ab_col8_batches.jsonl): B = 256 (two
 // slices of 128) 8.00 vs 8.05 ms per forward with col8_kernel; B = 128 (slices of 64) 4.35 vs 4.23 --
 // a persistent launch holding every CU keeps the other slice's kernels off the chip until it ends
 static int col8p_minb() {
   static const int v = env_int("MP_COL8P", 128);
-  return v;
-}
-// MP_COL8Q (default 0): 1 runs the software-pipelined form col8q_kernel instead of col8p_kernel (same
-// box, B = 256: 0.179 vs 0.170 ms; profiles/r6/ab/ab_col8.jsonl)
-static bool col8q_on() {
-  static const bool v = env_int("MP_COL8Q", 0) != 0;
-  return v;
-}
-// MP_COL8P_BF (default 1): the bf16 path's slices of >= MP_COL8P images run col8p_bf_kernel
-static bool col8p_bf_on() {
-  static const bool v = env_int("MP_COL8P_BF", 1) != 0;
   return v;
 }
 static int col8p_blocks() {
@@ -1465,7 +1245,7 @@ static int col8p_blocks() {
     int dev = 0, ncu = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
       ncu = 256;
-    return std::max(1, env_int("MP_COL8P_BLOCKS", ncu));
+    return std::max(1, ncu);
   }();
   return v;
 }
@@ -1475,15 +1255,6 @@ hipError_t launch_col_gemm(void* Z, const void* Gc, int B, float unscale, hipStr
   const int ngrp = (B + CG_NI - 1) / CG_NI;
   if (!bf && col8p_minb() > 0 && B >= col8p_minb()) {
     const int nitems = Z_CLS * ngrp, nblk = std::min(nitems, col8p_blocks());
-    if (col8q_on()) {
-      if (col8_znt(false, B, ntot))
-        hipLaunchKernelGGL((col8q_kernel<true>), dim3(nblk), dim3(512), 0, st, static_cast<cpx*>(Z),
-                           static_cast<const uint4*>(Gc), B, ngrp, nitems, unscale);
-      else
-        hipLaunchKernelGGL((col8q_kernel<false>), dim3(nblk), dim3(512), 0, st, static_cast<cpx*>(Z),
-                           static_cast<const uint4*>(Gc), B, ngrp, nitems, unscale);
-      return hipGetLastError();
-    }
     if (col8_znt(false, B, ntot))
       hipLaunchKernelGGL((col8p_kernel<true>), dim3(nblk), dim3(512), 0, st, static_cast<cpx*>(Z),
                          static_cast<const uint4*>(Gc), B, ngrp, nitems, unscale);
@@ -1492,7 +1263,7 @@ hipError_t launch_col_gemm(void* Z, const void* Gc, int B, float unscale, hipStr
                          static_cast<const uint4*>(Gc), B, ngrp, nitems, unscale);
     return hipGetLastError();
   }
-  if (bf && col8p_minb() > 0 && B >= col8p_minb() && col8p_bf_on()) {
+  if (bf && col8p_minb() > 0 && B >= col8p_minb()) {
     const int nitems = Z_CLS * ngrp, nblk = std::min(nitems, col8p_blocks());
     if (col8_znt(true, B, ntot))
       hipLaunchKernelGGL((col8p_bf_kernel<true>), dim3(nblk), dim3(512), 0, st, Z, static_cast<const uint4*>(Gc), B,

@@ -376,8 +376,8 @@ void ensure_ws(mp_ctx* c, int64_t n, int64_t H, int64_t W) {
 // MP_DTYPE_BF16 keeps the FFT loop's maps (X, O, I, Og, P2) in bf16 (k_fft.hip map_ld4)
 bool bf16_maps(const mp_ctx* c) { return c->dtype == MP_DTYPE_BF16 && fft_bf16_maps(); }
 
-// the drive X of an FFT-path context is a C4 map (k_fft.hip FFT_C4 bit 3)
-bool x_c4(const mp_ctx* c) { return is_fft(c->dtype) && fft_c4_drive(); }
+// the drive X of an FFT-path context is a C4 map (fft_dev.hpp)
+bool x_c4(const mp_ctx* c) { return is_fft(c->dtype); }
 
 // one association-field conv p_r * a.src with its fused hGRU epilogue, in the context's precision
 void eCRF_conv(mp_ctx* c, int epi, const ConvArgs& a, int n, hipStream_t st) {
@@ -599,22 +599,13 @@ void circuit_range(mp_ctx* c, int b0, int n, int ntot, int H, int W, int T, cons
       ProfScope ps(c, st, "conv15_b");
       eCRF_conv(c, EPI_HGRU_B, s.b, n, st);
     }
-    store_step(so, O, I, b0, n, H, W, t, bm, st, fft && fft_c4_maps(), fft && fft_c4_state());
+    store_step(so, O, I, b0, n, H, W, t, bm, st, fft, fft);
   }
 }
 
 // fc_1 on pre-split activation planes (MP_FC_PRESPLIT=0: the fp32 map + in-loop split, for A/B)
 bool fc_presplit() {
   static const bool v = env_int("MP_FC_PRESPLIT", 1) != 0;
-  return v;
-}
-
-// MP_FC_SLICE (A/B, default 0): 1 runs the pose head (fc_1, its reduce + BN_4, fc_out) per hGRU batch
-// slice on the slice's stream, right after that slice's loop, instead of once for the whole batch after
-// the join.  Bit-identical, but each slice streams fc_1's 1.07 GB of weights: same box, B = 256 8.16 vs
-// 7.97 ms, B = 64 2.60 vs 2.36 (profiles/r6/ab/ab_fc_slice.jsonl)
-bool fc_slice() {
-  static const bool v = env_int("MP_FC_SLICE", 0) != 0;
   return v;
 }
 
@@ -645,11 +636,8 @@ int slice_min() {
 // pre (optional): work a batch slice needs before its hGRU loop (the backbone of its images), run on the
 // slice's stream so that one slice's backbone overlaps another's loop
 using SliceFn = std::function<void(int b0, int cnt, hipStream_t s)>;
-// post (optional): work a batch slice does after its hGRU loop (the pose head on its rows), on the
-// slice's stream, so that the first slice's head overlaps the last slice's loop
 void run_circuit(mp_ctx* c, int64_t n, int H, int W, int T, const float* o0_nhwc, float* final_dst2,
-                 const StateOut* so, hipStream_t st, const SplitOut* sp = nullptr, const SliceFn* pre = nullptr,
-                 const SliceFn* post = nullptr) {
+                 const StateOut* so, hipStream_t st, const SplitOut* sp = nullptr, const SliceFn* pre = nullptr) {
   if (sp && !is_fft(c->dtype)) fail(MP_ERR_STATE, "split fc_1 planes are an FFT-path output");
   // FFT path, not profiling: batch slices are independent, so they run on separate streams and
   // their latency-bound kernels overlap (the per-kernel HIP-event profile keeps one stream)
@@ -707,7 +695,6 @@ void run_circuit(mp_ctx* c, int64_t n, int H, int W, int T, const float* o0_nhwc
     if (stagger && k + 1 < ns) hip_check(hipEventRecord(c->ev_pre, sl.s), "hipEventRecord");
     if (!multi) gate_init();   // one stream: after the backbone
     circuit_range(c, sl.b0, sl.cnt, (int)n, H, W, T, o0_nhwc, final_dst2, so, sp, sl.s);
-    if (post) (*post)(sl.b0, sl.cnt, sl.s);
   }
   for (int k = 1; k < (int)slices.size(); ++k) {
     hip_check(hipEventRecord(c->ev_join[k - 1], slices[k].s), "hipEventRecord");
@@ -1315,55 +1302,48 @@ int pose_fwd(mp_ctx* ctx, const float* depth, int64_t n, int64_t h, int64_t w, c
       sp.hi = reinterpret_cast<_Float16*>(ctx->fcin.p);
       sp.lo = fc_np == 3 ? sp.hi + (size_t)N * ctx->fc1_in : nullptr;
     }
-    // the head of rows b0 .. b0 + cnt on stream s: fc_1 in the context's form (exact fp32, f16x3 on the fp32
-    // map, or f16x3 on the split planes; partials in the rows' own S x cnt x Npad region of part, so slices
-    // run at once), relu + BN_4 into h1, fc_out (part2), its reduce into out.  Each row's sums are the same
-    // MFMA chains whatever the rows' count (the split count and slice length are functions of K and N
-    // only): a slice's head is bit-identical to its rows of the whole-batch head
-    int ks1, ks2;
-    const int S1 = fc_choose_splits(N, ctx->fc1_in, ctx->fc1_out, &ks1);
-    const int S2 = fc_choose_splits(N, ctx->fc1_out, ctx->nout, &ks2);
-    const size_t np1 = (size_t)(ctx->fc1_out + 31) / 32 * 32, np2 = (size_t)(ctx->nout + 31) / 32 * 32;
-    const SliceFn head = [&](int b0, int cnt, hipStream_t s) {
-      const size_t r1 = (size_t)b0 * ctx->fc1_in, r2 = (size_t)b0 * ctx->fc1_out;   // the rows' offsets
-      float* h1 = ctx->h1.f() + r2;
-      {
-        ProfScope ps(ctx, s, "fc1");
-        float* p1 = ctx->part.f() + (size_t)S1 * b0 * np1;
-        hip_check(ctx->dtype == MP_DTYPE_F32
-                      ? launch_fc_gemm(ctx->fcin.f() + r1, ctx->fc1_in, ctx->fc1_pk.v4(), p1, cnt, ctx->fc1_in,
-                                       ctx->fc1_out, S1, ks1, s)
-                  : presplit ? launch_fc_gemm_x3p(sp.hi + r1, sp.lo ? sp.lo + r1 : nullptr, ctx->fc1_in, ctx->fc1_pk.p,
-                                                  ctx->fc1_unscale, p1, cnt, ctx->fc1_in, ctx->fc1_out, S1, ks1, s, fc_np)
-                             : launch_fc_gemm_x3(ctx->fcin.f() + r1, ctx->fc1_in, ctx->fc1_pk.p, ctx->fc1_unscale, p1, cnt,
-                                                 ctx->fc1_in, ctx->fc1_out, S1, ks1, s, fc_np),
-                  "fc_1 gemm");
-        if (tp.fc1)   // fc_1 + bias before the relu (same partial sums)
-          hip_check(launch_fc_reduce(p1, S1, cnt, ctx->fc1_out, ctx->fc1_b.f(), 0, nullptr, nullptr, tp.fc1 + r2,
-                                     ctx->fc1_out, s),
-                    "fc1 tap");
-        hip_check(launch_fc_reduce(p1, S1, cnt, ctx->fc1_out, ctx->fc1_b.f(), 1, ctx->bn4_s.f(), ctx->bn4_t.f(), h1,
-                                   ctx->fc1_out, s),
-                  "fc_1 reduce");
-      }
-      ProfScope ps(ctx, s, "fc_out");
-      float* p2 = ctx->part2.f() + (size_t)S2 * b0 * np2;
-      hip_check(launch_fc_gemm(h1, ctx->fc1_out, ctx->fco_pk.v4(), p2, cnt, ctx->fc1_out, ctx->nout, S2, ks2, s),
-                "fc_out gemm");
-      hip_check(launch_fc_reduce(p2, S2, cnt, ctx->nout, ctx->fco_b.f(), 0, nullptr, nullptr, out + (size_t)b0 * ctx->nout,
-                                 ctx->nout, s),
-                "fc_out reduce");
-    };
-    // per hGRU slice on its stream (MP_FC_SLICE), or once for the whole batch after the join: the taps'
-    // copies sit around that one call
-    const bool head_slices = presplit && fc_slice() && !tp.fc1 && !tp.relu1;
     run_circuit(ctx, n, H, W, ctx->timesteps, h0, ctx->fcin.f(), sop, st, presplit ? &sp : nullptr,
-                bb_pipe ? &backbone : nullptr, head_slices ? &head : nullptr);
+                bb_pipe ? &backbone : nullptr);
     if (tp.hgru)
       hip_check(hipMemcpyAsync(tp.hgru, ctx->fcin.f(), (size_t)N * ctx->fc1_in * sizeof(float),
                                hipMemcpyDeviceToDevice, st),
                 "hgru tap");
-    if (!head_slices) head(0, N, st);
+    // the head, once for the whole batch after the join: fc_1 in the context's form (exact fp32, f16x3 on
+    // the fp32 map, or f16x3 on the split planes; partials in part), relu + BN_4 into h1, fc_out (part2), its
+    // reduce into out.  Each row's sums are the same MFMA chains whatever the rows' count (the split count
+    // and slice length are functions of K and N only).  Per hGRU slice on the slice's stream it measured
+    // slower, each slice streaming fc_1's 1.07 GB of weights: same box, B = 256 8.16 vs 7.97 ms, B = 64
+    // 2.60 vs 2.36 (profiles/r6/ab/ab_fc_*.jsonl)
+    int ks1, ks2;
+    const int S1 = fc_choose_splits(N, ctx->fc1_in, ctx->fc1_out, &ks1);
+    const int S2 = fc_choose_splits(N, ctx->fc1_out, ctx->nout, &ks2);
+    {
+      ProfScope ps(ctx, st, "fc1");
+      hip_check(ctx->dtype == MP_DTYPE_F32
+                    ? launch_fc_gemm(ctx->fcin.f(), ctx->fc1_in, ctx->fc1_pk.v4(), ctx->part.f(), N, ctx->fc1_in,
+                                     ctx->fc1_out, S1, ks1, st)
+                : presplit ? launch_fc_gemm_x3p(sp.hi, sp.lo, ctx->fc1_in, ctx->fc1_pk.p, ctx->fc1_unscale,
+                                                ctx->part.f(), N, ctx->fc1_in, ctx->fc1_out, S1, ks1, st, fc_np)
+                           : launch_fc_gemm_x3(ctx->fcin.f(), ctx->fc1_in, ctx->fc1_pk.p, ctx->fc1_unscale,
+                                               ctx->part.f(), N, ctx->fc1_in, ctx->fc1_out, S1, ks1, st, fc_np),
+                "fc_1 gemm");
+      if (tp.fc1)   // fc_1 + bias before the relu (same partial sums)
+        hip_check(launch_fc_reduce(ctx->part.f(), S1, N, ctx->fc1_out, ctx->fc1_b.f(), 0, nullptr, nullptr, tp.fc1,
+                                   ctx->fc1_out, st),
+                  "fc1 tap");
+      hip_check(launch_fc_reduce(ctx->part.f(), S1, N, ctx->fc1_out, ctx->fc1_b.f(), 1, ctx->bn4_s.f(),
+                                 ctx->bn4_t.f(), ctx->h1.f(), ctx->fc1_out, st),
+                "fc_1 reduce");
+    }
+    {
+      ProfScope ps(ctx, st, "fc_out");
+      hip_check(launch_fc_gemm(ctx->h1.f(), ctx->fc1_out, ctx->fco_pk.v4(), ctx->part2.f(), N, ctx->fc1_out,
+                               ctx->nout, S2, ks2, st),
+                "fc_out gemm");
+      hip_check(launch_fc_reduce(ctx->part2.f(), S2, N, ctx->nout, ctx->fco_b.f(), 0, nullptr, nullptr, out,
+                                 ctx->nout, st),
+                "fc_out reduce");
+    }
     if (tp.relu1)
       hip_check(hipMemcpyAsync(tp.relu1, ctx->h1.f(), (size_t)N * ctx->fc1_out * sizeof(float),
                                hipMemcpyDeviceToDevice, st),

@@ -28,7 +28,7 @@ inline int env_int(const char* name, int dflt) {
 __device__ __forceinline__ size_t c8_index(int b, int q, int y, int x, int e, int H, int W) {
   return ((((size_t)b * NQ + q) * H + y) * W + x) * 8 + e;
 }
-// C4 [N][16 channel groups][H][W][4]: the FFT loop's P2, I, O and X maps (k_fft.hip pp_index, ii_index,
+// C4 [N][16 channel groups][H][W][4]: the FFT loop's P2, I, O and X maps (fft_dev.hpp pp_index, ii_index,
 // oo_index, xx_index), written per 4-channel group by the inverse FFT kernels as one contiguous run;
 // channel 8 q + e of the C8 naming.  W must be a power of two: the C4_SWZ swizzle x ^ (W / 2) maps
 // [0, W) onto itself only then (the FFT path's maps are 32 or 64 wide; launchers check c4_width_ok)

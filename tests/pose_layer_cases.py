@@ -104,8 +104,6 @@ SWITCH_ROWS = {
     "MP_FC_BK64=0": (("bb_32x32", "bf16", 3), ("bb_64x32", "bf16", 65),
                      ("head_32x32_w160", "bf16", 130), ("head_16x32_w1024", "bf16", 65)),
     "MP_FC_PRESPLIT=0": _DEFAULT_SWITCH,
-    "MP_FC_SLICE=1": (("bb_32x32", "fp32_fft", 3), ("bb_64x32", "bf16", 65),   # slices of 96 + 34 and 96 + 33 rows
-                      ("head_32x32_w160", "fp32_fft", 130), ("head_16x32_w1024", "bf16", 129)),
     "MP_BB_PIPE=0": _DEFAULT_SWITCH,
 }
 

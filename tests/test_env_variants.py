@@ -151,12 +151,6 @@ BITS_CASES = [
     # step 0 reading O0 (NHWC) directly, or row(INIT) copying it into the C8 state map first
     ("pose80", "fp32_fft", "MP_O0_DIRECT", ("0", "1"), {}),
     ("pose12", "fp32_fft", "MP_O0_DIRECT", ("0", "1"), {}),
-    # the pose head per batch slice on the slice's stream, or once after the join (64 + 16 crops)
-    ("pose80", "fp32_fft", "MP_FC_SLICE", ("0", "1"), {}),
-    ("pose80", "bf16", "MP_FC_SLICE", ("0", "1"), {}),
-    # col8q_kernel (software-pipelined) or col8p_kernel: one item's arithmetic either way
-    ("pose80", "fp32_fft", "MP_COL8Q", ("0", "1"), {"MP_COL8P": "1"}),
-    ("pose12", "fp32_fft", "MP_COL8Q", ("0", "1"), {"MP_COL8P": "1"}),
     # row A on channel quarters (rowq_a_kernel) or as row8_kernel<ROW_A>: one batch slice of 12, and
     # two slices (64 + 16) all on rowq; and the cache policy of a cache-resident batch (12 crops)
     ("pose12", "fp32_fft", "MP_ROWQ_MAXB", ("0", "16"), {}),

@@ -24,7 +24,6 @@ def test_every_row_has_a_shape_the_library_accepts():
         for nm, d, n in rows:
             assert d in P.ROWS[nm].dtypes and (n in P.ROWS[nm].ns or nm.startswith("bb")), (var, nm, d, n)
     assert all(d == "bf16" for _, d, _ in P.SWITCH_ROWS["MP_FC_BK64=0"])
-    assert ("head_32x32_w160", "fp32_fft", 130) in P.SWITCH_ROWS["MP_FC_SLICE=1"]
     # the tile choices the rows name: conv_small_tiles' 128-workgroup limit of the 32-row tiling
     wg = lambda r, n: n * (r.W // 32) * (r.H // 32)
     assert wg(P.ROWS["bb_32x32"], 3) <= 128 < wg(P.ROWS["bb_32x32"], 129)

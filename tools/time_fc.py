@@ -33,5 +33,5 @@ for B in a.batch:
     ms, n = ctx.profile_read("fc1")
     for k in ("backbone", "conv15_a", "conv15_b", "fc_out", "fft_fwd", "spec_gemm", "inv_a_fwd", "fft_inv", "epi_b"):
         ctx.profile_read(k)
-    print(f"KSLICE={os.environ.get('MP_FC_KSLICE', 'default')} dtype={a.dtype} B={B}: fc1 {ms / n:.4f} ms/launch "
+    print(f"dtype={a.dtype} B={B}: fc1 {ms / n:.4f} ms/launch "
           f"out[0,:2]={out[0, :2].tolist()}")
