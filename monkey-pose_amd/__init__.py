@@ -17,6 +17,8 @@ The directory name carries a hyphen, so import it with ``importlib.import_module
   host, ``mp_real_frames_dev`` on the device, the same bits); ``render_overlays`` (depth frames
   through a colour table with joint markers and bones drawn on them: ``mp_overlay_dev``) and
   ``render_overlays_np`` (the same rule in numpy)
+* ``png``         -- ``encode_png`` / ``png_files`` / ``png_bound``: PNG files from RGB pictures, on the device
+  (``mp_png_encode_dev``) or, for numpy input, by the same byte rule on the host (``include/monkeypose_png.h``)
 * ``pose_evaluation`` -- the pose metrics (``getMeanError_np`` ...) on numpy arrays and on CUDA tensors,
   ``PoseEvaluator`` (a streaming evaluator in device memory)
 * ``weights``     -- TF variable-name tables and deterministic synthetic initialisers
@@ -33,6 +35,7 @@ from . import train_hier_networks  # noqa: F401
 from . import train_dense_hier_networks  # noqa: F401
 from . import train_cnn_networks_hgru  # noqa: F401
 from . import monkeydetector  # noqa: F401
+from . import png  # noqa: F401
 from . import pose_evaluation  # noqa: F401
 from . import parallel  # noqa: F401
 from . import tf_checkpoint  # noqa: F401

@@ -271,5 +271,9 @@ hipError_t launch_eval_reset(void* state, int J, int T, const float* thresholds_
 hipError_t launch_eval_accumulate(void* state, const float* labels, const float* results, int64_t n, int J, int T,
                                   float scale, float* dist, float* frame_mean, float* frame_max, hipStream_t st);
 hipError_t launch_eval_summary(const void* state, int J, int T, double* out, hipStream_t st);
+// k_png.hip (PNG files from RGB pictures; the byte rule is png_rule.hpp)
+size_t png_work_bytes(int64_t n, int h, int w);
+hipError_t launch_png_encode(const uint8_t* rgb, int64_t n, int h, int w, uint8_t* out, int64_t out_stride,
+                             int64_t* sizes, void* work, hipStream_t st);
 
 }  // namespace mp

@@ -236,6 +236,12 @@ class FramePosePipeline:
             raise RuntimeError("render() draws the frames of the last run(): call run() first")
         return render_overlays(self._last_frames, joints_uvd, **kw)
 
+    def render_png(self, joints_uvd, **render_kw):
+        """``render(...)`` followed by ``png.encode_png`` on the same stream: the pictures as finished PNG
+        files in device memory -> (buf [n, png_bound(h, w)] uint8, sizes [n] int64), CUDA tensors reused by
+        the next call of the same shape; ``png.png_files(buf, sizes)`` copies the files to the host."""
+        return _render_png(self, dict(render_kw, joints_uvd=joints_uvd))
+
 
 class ValidationPipeline:
     """The validation pass of ``train_model`` (train_cnn_networks_hgru.py:160-173, 229-237) and of
@@ -314,6 +320,12 @@ def evaluate_tfrecord(tfrecord_file, pipeline: ValidationPipeline, batch_size, m
     return pipeline.summary()
 
 
+def _render_png(pipeline, render_kw):
+    """``pipeline.render(**render_kw)`` followed by ``png.encode_png`` on the same stream"""
+    from .png import encode_png
+    return encode_png(pipeline.render(**render_kw), stream=render_kw.get("stream"))
+
+
 def _render_sets(frames, uvd, extra_sets, kw):
     """``render_overlays`` of ``frames`` with ``uvd`` as set 0 and ``extra_sets`` drawn over it"""
     import torch
@@ -355,6 +367,12 @@ class DetectorPosePipeline:
         if self._last is None:
             raise RuntimeError("render() draws the frames of the last run(): call run() first")
         return _render_sets(self._last[0], self._last[1], extra_sets, kw)
+
+    def render_png(self, **render_kw):
+        """``render(...)`` followed by ``png.encode_png`` on the same stream: the pictures as finished PNG
+        files in device memory -> (buf [n, png_bound(h, w)] uint8, sizes [n] int64), CUDA tensors reused by
+        the next call of the same shape; ``png.png_files(buf, sizes)`` copies the files to the host."""
+        return _render_png(self, render_kw)
 
     def run(self, frames, h2_init=None):
         import torch
@@ -448,8 +466,15 @@ class RealDataPipeline:
             depth_range = (0.0, 1.0) if self.gate is None else (self.gate[0] / md, self.gate[1] / md)
         return _render_sets(self._frames, self._out[1], extra_sets, dict(kw, bones=bones, depth_range=depth_range))
 
+    def render_png(self, **render_kw):
+        """``render(...)`` followed by ``png.encode_png`` on the same stream: the pictures as finished PNG
+        files in device memory -> (buf [n, png_bound(h, w)] uint8, sizes [n] int64), CUDA tensors reused by
+        the next call of the same shape; ``png.png_files(buf, sizes)`` copies the files to the host."""
+        return _render_png(self, render_kw)
 
-def eval_model_on_real_data(real_data_dir, pipeline, batch_size=16, device=None, overlay=None, overlay_args=None):
+
+def eval_model_on_real_data(real_data_dir, pipeline, batch_size=16, device=None, overlay=None, overlay_args=None,
+                            overlay_png=None):
     """``eval_model_on_real_data`` (train_cnn_networks_hgru.py:342-419) over a directory of recorded
     frames: the files ``sorted(glob(real_data_dir + '*.npy'))`` (the reference's pattern: the directory
     ends in its separator), each loaded on the host, stacked ``batch_size`` at a time, uploaded as they
@@ -461,7 +486,11 @@ def eval_model_on_real_data(real_data_dir, pipeline, batch_size=16, device=None,
     The reference's plot of every frame (409-415) is ``overlay``: a callback called once per batch with
     ``(files, rgb)``, the batch's file names and ``pipeline.render(**overlay_args)`` copied to the host
     as a numpy uint8 [n, h, w, 3] array (the depth frame through a colour table, the joints drawn on
-    it).  ``None``: nothing is drawn; the four returned values are the same either way."""
+    it).  ``None``: nothing is drawn; the four returned values are the same either way.
+
+    ``overlay_png`` is the same picture as a finished file: a callback called once per batch with
+    ``(files, pngs)``, ``pngs`` a list of ``bytes``, one PNG file a frame, encoded on the device
+    (``pipeline.render_png(**overlay_args)``): only the compressed bytes cross to the host."""
     import glob
     import torch
     files = sorted(glob.glob(real_data_dir + '*.npy'))
@@ -491,6 +520,9 @@ def eval_model_on_real_data(real_data_dir, pipeline, batch_size=16, device=None,
             acc.append(t.detach().cpu().numpy().copy())     # a copy: the pipeline reuses its buffers
         if overlay is not None:
             overlay(files[i:i + batch_size], pipeline.render(**(overlay_args or {})).cpu().numpy())
+        if overlay_png is not None:
+            from .png import png_files
+            overlay_png(files[i:i + batch_size], png_files(*pipeline.render_png(**(overlay_args or {}))))
     return files, np.concatenate(xyz), np.concatenate(uvd), np.concatenate(coms)
 
 

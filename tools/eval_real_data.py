@@ -8,6 +8,9 @@ files.txt (one path per line, the order of the arrays' rows) into --out-dir.  Wi
 writes overlay_%05d.png, one picture per frame in that order: the gated depth frame through a colour
 table with the joints drawn on it on the device (RealDataPipeline.render; what the reference shows with
 plt.imshow / plt.scatter), and with --bones FILE.json (a list of joint index pairs) the skeleton lines.
+With --device-png as well, those files are encoded on the device too (RealDataPipeline.render_png,
+monkey-pose_amd/png.py): only the finished files' bytes cross to the host, where they are written as
+they are.  The same pixels; larger files (fixed Huffman codes), no host deflate.
 
 The models get the variables of --checkpoint DIR (a TF checkpoint holding the attention and the pose
 variables), or synthetic weights.  Without a directory it first writes --frames synthetic recordings
@@ -18,7 +21,7 @@ stops on the child's failure.
 
     python tools/eval_real_data.py [DIR] [--batch 16] [--model cnn|hgru] [--checkpoint DIR]
                                    [--out-dir real_eval] [--no-gate] [--plain]
-                                   [--overlay] [--bones FILE.json] [--lut gray|jet]
+                                   [--overlay] [--device-png] [--bones FILE.json] [--lut gray|jet]
 """
 import argparse
 import importlib
@@ -102,8 +105,15 @@ def child(a):
             write_png(os.path.join(a.out_dir, "overlay_%05d.png" % len(drawn)), img)
             drawn.append(1)
 
+    def overlay_png(batch_files, pngs):
+        for data in pngs:
+            with open(os.path.join(a.out_dir, "overlay_%05d.png" % len(drawn)), "wb") as f:
+                f.write(data)
+            drawn.append(1)
+
     files, xyz, uvd, coms = T.eval_model_on_real_data(
-        a.dir, pipe, batch_size=a.batch, overlay=overlay if a.overlay else None,
+        a.dir, pipe, batch_size=a.batch, overlay=overlay if a.overlay and not a.device_png else None,
+        overlay_png=overlay_png if a.overlay and a.device_png else None,
         overlay_args=dict(bones=read_bones(a.bones), lut=a.lut))
     torch.cuda.synchronize()
     os.makedirs(a.out_dir, exist_ok=True)
@@ -131,6 +141,8 @@ def main():
     ap.add_argument("--plain", action="store_true", help="the frames are stored [h, w] already")
     ap.add_argument("--no-check", action="store_true", help="do not read the crop status back per batch")
     ap.add_argument("--overlay", action="store_true", help="write overlay_%%05d.png, one picture per frame")
+    ap.add_argument("--device-png", action="store_true",
+                    help="with --overlay: encode the PNG files on the device (RealDataPipeline.render_png)")
     ap.add_argument("--bones", help="JSON file of joint index pairs: the skeleton lines of --overlay")
     ap.add_argument("--lut", choices=["gray", "jet"], default="gray", help="the colour table of --overlay")
     ap.add_argument("--frames", type=int, default=8, help="synthetic recordings to write when no directory is given")
@@ -152,7 +164,7 @@ def main():
     cmd += ["--bones", a.bones] if a.bones else []
     cmd += ["--checkpoint", a.checkpoint] if a.checkpoint else []
     for flag, on in (("--no-gate", a.no_gate), ("--plain", a.plain), ("--no-check", a.no_check),
-                     ("--overlay", a.overlay)):
+                     ("--overlay", a.overlay), ("--device-png", a.device_png)):
         cmd += [flag] if on else []
     try:
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=CHILD_LIMIT_S)

@@ -12,12 +12,21 @@ J = 23, two joint sets and a 22-bone chain, p50 over --calls calls after warm-up
   (c) pipeline    RealDataPipeline.run alone, run + render + the D2H of the RGB bytes, and the host
                   route the render replaces: D2H of the float32 frames and uvd, then render_overlays_np
 
+  (d) --png       the picture path's last step, after `run`, B frames a call: the host route (render, D2H
+                  of the RGB into pinned memory, then tools/eval_real_data.py write_png's compress call per
+                  frame on one thread; file writes excluded) against the device route (render_png, then
+                  png.png_files: D2H of sizes and of the used columns); the encode alone and its two
+                  kernels' sum from device events; the files' sizes against zlib levels 6 and 1; and the
+                  encode against its byte floor (raw bytes read + file bytes written at the box's copy
+                  rate).  Written to profiles/png/time_png.json
+
 The forms alternate in rounds, so that drift of the shared host hits all of them alike.  Host-clock
 timings end in a device synchronise.  Every step runs in a child process of its own under its own
 time limit, and the first failure stops the run; the parent never touches the GPU.  One JSON goes to
 profiles/overlay/, stamped with bench.tree_stamp.
 
     python tools/time_overlay.py [--calls 100] [--batch 256] [--out profiles/overlay/time_overlay.json]
+    python tools/time_overlay.py --png [--calls 20] [--batch 256] [--out profiles/png/time_png.json]
 """
 import argparse
 import importlib
@@ -33,7 +42,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 CAM = (365.456, 365.456, 256, 212, [800, 800, 1200], 200, 10000)   # train_cnn_networks_hgru.py:345
 COM_NORM = (0.5, 0.5, 0.13)        # afc_out: zero weights, these biases -- every crop is valid
-STEP_LIMIT_S = {"batch": 540, "hbm": 240}
+STEP_LIMIT_S = {"batch": 540, "hbm": 240, "png": 540}
 HBM_MIB = (128, 512, 2048)
 BONES = [(k, k + 1) for k in range(22)]
 
@@ -192,6 +201,78 @@ def step_batch(B, calls):
     return res
 
 
+def step_png(B, calls):
+    """(d): the host route and the device route of the PNG files of one batch, after `run`"""
+    import zlib
+    import torch
+    mp = importlib.import_module("monkey-pose_amd")
+    W, T, M, P = mp.weights, mp.train_cnn_networks_hgru, mp.monkeydetector, mp.png
+    dev = torch.device("cuda", 0)
+    md = M.MonkeyDetector(*CAM)
+    base = W.synth_frames(min(B, 16), seed=14)[..., 0]
+    mm = np.round(base * np.float32(10000.0)).astype(np.uint16)
+    mm = mm[np.arange(B) % mm.shape[0]]
+    raw_d = torch.from_numpy(np.ascontiguousarray(mm.transpose(0, 2, 1))).to(dev)
+    n, h, w = mm.shape
+    sync = lambda: torch.cuda.synchronize(dev)
+    aw = W.attn_synth_weights(seed=1234)
+    aw["cnn/afc_out/afc_out_weights"] = np.zeros((1024, 3), np.float32)
+    aw["cnn/afc_out/afc_out_biases"] = np.asarray(COM_NORM, np.float32)
+    attn = T.attn_model_struct()
+    attn.load_weights(aw)
+    pose = T.cnn_model_struct()
+    pose.load_weights(W.synth_weights(W.cnn_vars(output_shape=69, crop=128), seed=77))
+    pipe = T.RealDataPipeline(attn, pose, md, T.InferenceConfig())
+    pipe.run(raw_d)
+    sync()
+    rgb_dev = torch.empty((B, h, w, 3), dtype=torch.uint8, device=dev)
+    rgb_host = torch.empty((B, h, w, 3), dtype=torch.uint8).pin_memory()
+    res = {"batch": B, "hw": [h, w], "joints": 23, "sets": 1, "bones": len(BONES), "luts": {}}
+    for lut in ("gray", "jet"):
+        kw = dict(bones=BONES, lut=lut)
+        rows = np.zeros((h, 1 + 3 * w), np.uint8)
+        z6 = []
+
+        def host_route():
+            rgb_host.copy_(pipe.render(out=rgb_dev, **kw), non_blocking=True)
+            sync()
+            z6.clear()
+            for img in rgb_host.numpy():
+                rows[:, 1:] = img.reshape(h, 3 * w)
+                z6.append(len(zlib.compress(rows.tobytes(), 6)))          # write_png's IDAT body
+
+        files = []
+
+        def device_route():
+            files[:] = P.png_files(*pipe.render_png(out=rgb_dev, **kw))
+
+        acc = {"host": [], "device": []}
+        for r in range(3):                                                 # alternated rounds
+            acc["host"].append(host_timed(host_route, 1, 1 if r == 0 else 0, sync))
+            acc["device"].append(host_timed(device_route, max(1, calls // 3), 2 if r == 0 else 0, sync))
+        th, td = p50(np.concatenate(acc["host"])), p50(np.concatenate(acc["device"]))
+        rgb = pipe.render(out=rgb_dev, **kw)
+        enc = event_timed(lambda: P.encode_png(rgb), calls, 3, torch)
+        ren = event_timed(lambda: pipe.render(out=rgb_dev, **kw), calls, 3, torch)
+        few = rgb_host.numpy()[:4]
+        hb, hs = P.encode_png(few)
+        sizes = np.asarray([len(f) for f in files])
+        z1 = []
+        for img in few:
+            rows[:, 1:] = img.reshape(h, 3 * w)
+            z1.append(len(zlib.compress(rows.tobytes(), 1)))
+        res["luts"][lut] = {
+            "host_route_ms": round(th, 2), "host_route_all_ms": [round(float(x), 2) for x in np.concatenate(acc["host"])],
+            "device_route_ms": round(td, 3), "device_route_samples": int(sum(len(x) for x in acc["device"])),
+            "host_over_device": round(th / td, 1), "render_event_ms": round(ren, 4), "encode_event_ms": round(enc, 4),
+            "raw_bytes": int(B * h * (1 + 3 * w)), "file_bytes": int(sizes.sum()),
+            "file_bytes_per_frame": int(sizes.mean()), "bound_per_frame": P.png_bound(h, w),
+            "zlib6_idat_bytes_per_frame": int(np.mean(z6)), "zlib1_idat_bytes_per_frame_first4": int(np.mean(z1)),
+            "device_equals_host_first4": bool(files[:4] == P.png_files(hb, hs)),
+        }
+    return res
+
+
 def step_hbm():
     mp = importlib.import_module("monkey-pose_amd")
     return {str(mib): mp._lib.hbm_probe(0, mib << 20) for mib in HBM_MIB}
@@ -201,16 +282,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=100)
     ap.add_argument("--batch", type=int, default=256)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "overlay", "time_overlay.json"))
+    ap.add_argument("--out")
+    ap.add_argument("--png", action="store_true", help="the PNG leg (d) instead of (a)-(c)")
     ap.add_argument("--step", choices=sorted(STEP_LIMIT_S))
     a = ap.parse_args()
     if a.step:                                   # a child: one step, one JSON line
-        r = step_hbm() if a.step == "hbm" else step_batch(a.batch, a.calls)
+        r = step_hbm() if a.step == "hbm" else step_png(a.batch, a.calls) if a.step == "png" else step_batch(a.batch, a.calls)
         print("RESULT " + json.dumps(r), flush=True)
         return 0
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "png" if a.png else "overlay", "time_png.json" if a.png else "time_overlay.json")
     import bench
-    doc = {"tool": "tools/time_overlay.py", "tree_stamp": bench.tree_stamp(), "camera": list(CAM)}
-    for step in ("batch", "hbm"):
+    doc = {"tool": "tools/time_overlay.py" + (" --png" if a.png else ""), "tree_stamp": bench.tree_stamp(), "camera": list(CAM)}
+    for step in (("png", "hbm") if a.png else ("batch", "hbm")):
         try:
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--step", step, "--calls", str(a.calls),
                                 "--batch", str(a.batch)], capture_output=True, text=True, timeout=STEP_LIMIT_S[step])
@@ -223,6 +307,21 @@ def main():
             return p.returncode or 1
         doc[step] = json.loads(lines[-1][7:])
         print(step, json.dumps(doc[step]), flush=True)
+    if a.png:                                    # the encode against raw bytes in + file bytes out at the copy rate
+        for lut, v in doc["png"]["luts"].items():
+            v["encode_byte_floor_by_probe_MiB"] = {}
+            for mib, r in doc["hbm"].items():
+                fl = (v["raw_bytes"] + v["file_bytes"]) / r["copy_GBps"] / 1e6
+                v["encode_byte_floor_by_probe_MiB"][mib] = {"floor_ms": round(fl, 5),
+                                                            "encode_over_floor": round(v["encode_event_ms"] / fl, 2)}
+        doc["faster"] = all(v["device_route_ms"] < v["host_route_ms"] for v in doc["png"]["luts"].values())
+        doc["equal"] = all(v["device_equals_host_first4"] for v in doc["png"]["luts"].values())
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(doc, f, indent=1)
+            f.write("\n")
+        print("wrote", a.out, "device route faster =", doc["faster"], "equal =", doc["equal"])
+        return 0 if doc["faster"] and doc["equal"] else 1
     # the kernels' byte floors under the box's own streaming roofs (per probe size)
     floors = {}
     for mib, r in doc["hbm"].items():
