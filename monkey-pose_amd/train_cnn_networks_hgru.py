@@ -490,16 +490,25 @@ def eval_model_on_real_data(real_data_dir, pipeline, batch_size=16, device=None,
 
     ``overlay_png`` is the same picture as a finished file: a callback called once per batch with
     ``(files, pngs)``, ``pngs`` a list of ``bytes``, one PNG file a frame, encoded on the device
-    (``pipeline.render_png(**overlay_args)``): only the compressed bytes cross to the host."""
+    (``pipeline.render_png(**overlay_args)``): only the compressed bytes cross to the host.
+
+    A directory with no ``.npy`` file but ``*.png`` frames (the reference importer's ``depth_*.png``)
+    is read as PNG files: every file's IHDR is checked up front (one shape, one of gray16 / gray8), and
+    each batch's files are uploaded as they are and decoded on the device (``png.decode_png``), so only
+    the compressed bytes cross.  PNG frames are [h, w]: a pipeline built with ``transposed=True``
+    raises ``ValueError`` before any frame is run."""
     import glob
     import torch
     files = sorted(glob.glob(real_data_dir + '*.npy'))
-    if not files:
+    pngs = [] if files else sorted(glob.glob(real_data_dir + '*.png'))
+    if not files and not pngs:
         raise ValueError(f"no .npy frames match {real_data_dir + '*.npy'!r}")
     batch_size = int(batch_size)
     if batch_size <= 0:
         raise ValueError(f"batch_size must be positive, got {batch_size}")
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if pngs:
+        return _eval_png_frames(pngs, pipeline, batch_size, dev, overlay, overlay_args, overlay_png)
     first = None
     for f in files:                              # the headers alone, before any frame is run
         a = np.load(f, mmap_mode="r", allow_pickle=False)
@@ -523,6 +532,46 @@ def eval_model_on_real_data(real_data_dir, pipeline, batch_size=16, device=None,
         if overlay_png is not None:
             from .png import png_files
             overlay_png(files[i:i + batch_size], png_files(*pipeline.render_png(**(overlay_args or {}))))
+    return files, np.concatenate(xyz), np.concatenate(uvd), np.concatenate(coms)
+
+
+def _eval_png_frames(files, pipeline, batch_size, dev, overlay, overlay_args, overlay_png):
+    """eval_model_on_real_data over PNG frames: IHDRs first, then batch by batch upload -> decode -> run"""
+    import torch
+    from . import png
+    if getattr(pipeline, "transposed", False):
+        raise ValueError("PNG frames are stored [h, w]: build the pipeline with transposed=False")
+    first = None
+    for f in files:                              # the IHDRs alone, before any frame is run
+        with open(f, "rb") as fh:
+            try:
+                info = png.png_info(fh.read(33))
+            except ValueError as e:
+                raise ValueError(f"{f}: {e}") from None
+        if first is None:
+            if info[2] not in ("gray16", "gray8"):
+                raise ValueError(f"{f}: expected a 16- or 8-bit grayscale PNG frame, not interlaced")
+            first = info
+        elif info != first:
+            raise ValueError(f"{f}: frame is {info[2]} {info[:2]}, but {files[0]} is {first[2]} {first[:2]}; "
+                             "all frames of a directory must share one shape and format")
+    h, w, fmt = first
+    xyz, uvd, coms = [], [], []
+    for i in range(0, len(files), batch_size):
+        names = files[i:i + batch_size]
+        try:
+            frames = png.decode_png_files(names, device=dev, format=fmt)
+        except ValueError as e:
+            raise ValueError(f"{names[0]} ... {names[-1]}: {e}") from None
+        if frames.shape[1:] != (h, w):
+            raise ValueError(f"{names[0]}: decoded {tuple(frames.shape[1:])}, expected {(h, w)}")
+        res = pipeline.run(frames if fmt == "gray16" else frames.to(torch.uint16))
+        for acc, t in zip((xyz, uvd, coms), res[:3]):
+            acc.append(t.detach().cpu().numpy().copy())     # a copy: the pipeline reuses its buffers
+        if overlay is not None:
+            overlay(names, pipeline.render(**(overlay_args or {})).cpu().numpy())
+        if overlay_png is not None:
+            overlay_png(names, png.png_files(*pipeline.render_png(**(overlay_args or {}))))
     return files, np.concatenate(xyz), np.concatenate(uvd), np.concatenate(coms)
 
 

@@ -95,7 +95,10 @@ def child(a):
                  else W.cnn_vars(output_shape=cfg.num_classes, crop=128))
         pose.load_weights(W.synth_weights(table, seed=a.seed + 1))
     gate = None if a.no_gate else (a.gate_lo, a.gate_hi)
-    pipe = T.RealDataPipeline(attn, pose, md, cfg, gate=gate, fill=a.fill, transposed=not a.plain,
+    # a directory of depth_*.png frames (no .npy): PNG frames are stored [h, w] and decoded on the device
+    import glob
+    png_dir = not glob.glob(a.dir + "*.npy") and bool(glob.glob(a.dir + "*.png"))
+    pipe = T.RealDataPipeline(attn, pose, md, cfg, gate=gate, fill=a.fill, transposed=not a.plain and not png_dir,
                               check_crops=not a.no_check)
     os.makedirs(a.out_dir, exist_ok=True)
     drawn = []
@@ -129,7 +132,7 @@ def child(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("dir", nargs="?", help="directory of *.npy frames (the reference's config.real_data_dir)")
+    ap.add_argument("dir", nargs="?", help="directory of *.npy frames (the reference's config.real_data_dir), or of 16-bit *.png frames")
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--model", choices=["cnn", "hgru"], default="cnn")
     ap.add_argument("--checkpoint")
