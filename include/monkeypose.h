@@ -336,6 +336,28 @@ int mp_hier_fwd(mp_ctx* ctx, const float* depth, int64_t n, int64_t h, int64_t w
  *   out    [n, output_shape] (u, v, d) / (image_orig_size[0], image_orig_size[1], image_max_depth) */
 int mp_attn_fwd(mp_ctx* ctx, const float* frames, int64_t n, int64_t h, int64_t w, float* out, void* stream);
 
+/* the attention net's readable intermediates (train_cnn_networks_hgru.py:439-512); each a caller-owned
+ * device buffer, NULL = not wanted.  NHWC fp32.  aconv_1 is fused with its pool, so there is no conv1. */
+typedef struct {
+  float* resized;  /* [n, 128, 128, 1]    the resized input (the frames themselves at 128 x 128)  (439)     */
+  float* conv2;    /* [n, 64, 64, 128]    relu(aconv_2 + b), before the pool                      (452)     */
+  float* conv3;    /* [n, 32, 32, 256]    relu(aconv_3 + b)                                       (464)     */
+  float* conv4;    /* [n, 16, 16, 512]    relu(aconv_4 + b)                                       (476)     */
+  float* conv5;    /* [n, 8, 8, 1024]     relu(aconv_5 + b)                                       (488)     */
+  float* pool1;    /* [n, 64, 64, 64]     BN(max_pool(relu(aconv_1 + b)))                         (440-450) */
+  float* pool2;    /* [n, 32, 32, 128]    BN(max_pool(conv2))                                     (453-462) */
+  float* pool3;    /* [n, 16, 16, 256]    BN(max_pool(conv3))                                     (465-474) */
+  float* pool4;    /* [n, 8, 8, 512]      BN(max_pool(conv4))                                     (477-486) */
+  float* pool5;    /* [n, 4, 4, 1024]     BN(max_pool(conv5)), the afc_1 input                    (489-498) */
+  float* relu1;    /* [n, 1024]           BN(relu(afc_1))                                         (500-512) */
+} mp_attn_taps;
+
+/* mp_attn_fwd that also writes the requested intermediates (taps may be NULL: exactly mp_attn_fwd's
+ * launches).  Each tap is copied on `stream` right after its producer, before its buffer is reused.
+ * After a forward, mp_info "attn_path:<aconv_2 .. aconv_5>" reports the kernel each conv took. */
+int mp_attn_fwd_taps(mp_ctx* ctx, const float* frames, int64_t n, int64_t h, int64_t w, float* out,
+                     const mp_attn_taps* taps, void* stream);
+
 /* tf.image.resize_images(x, [ho, wo]) with the TF1 defaults (BILINEAR, align_corners=False,
  * legacy source coordinates in = out * in_size / out_size), bit-identical to TF's float32 kernel:
  *   x [n, h, w, c] -> out [n, ho, wo, c], device pointers */
@@ -547,7 +569,9 @@ int mp_eval_summary_dev(const void* state, int64_t joints, int64_t T, double* ou
  * "graph_streams" (streams the schedule uses), "graph_buffers" (activation buffers after concat placement), "graph_fused_pools" (2x2 max pools
  * computed inside their conv's kernel: MP_GRAPH_FUSE / MP_GRAPH_FUSE_POOL), "graph_fused_1x1" (1x1
  * convs computed by a sibling's kernel) and "graph_path:<conv layer scope>" (the kernel the planned
- * conv launches, an MP_PATH_* word, below) -- as planned by the last forward */
+ * conv launches, an MP_PATH_* word, below) -- as planned by the last forward; attention contexts
+ * "attn_path:<aconv_2 .. aconv_5>" (the same word for the conv of that scope, from its launch arguments
+ * at the last forward's batch; aconv_1 is the fused MP_PATH_CONV1_POOL_BN kernel) */
 int mp_info(mp_ctx* ctx, const char* key, int64_t* value);
 
 /* "graph_path:<scope>": which kernel family the planned conv of that scope launches, as decided by

@@ -153,6 +153,8 @@ _SIGS = {
                                    ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]),
     "mp_attn_fwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                    ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "mp_attn_fwd_taps": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                        ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "mp_resize_bilinear": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                           ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
                                           ctypes.c_void_p]),
@@ -194,6 +196,15 @@ MP_ABI_VERSION = (0, 2)
 
 class PoseTaps(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in TAP_NAMES]
+
+
+# mp_attn_taps field order (include/monkeypose.h)
+ATTN_TAP_NAMES = ("resized", "conv2", "conv3", "conv4", "conv5", "pool1", "pool2", "pool3", "pool4", "pool5",
+                  "relu1")
+
+
+class AttnTaps(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ATTN_TAP_NAMES]
 
 
 class FwdOpts(ctypes.Structure):
@@ -421,6 +432,21 @@ class Context:
     def attn_fwd(self, frames, out, stream: int) -> None:
         n, h, w, c = frames.shape
         check(self.lib.mp_attn_fwd(self.h, _ptr(frames), n, h, w, _ptr(out), ctypes.c_void_p(stream)))
+
+    def attn_fwd_taps(self, frames, out, taps: dict, stream: int) -> None:
+        """mp_attn_fwd_taps; ``taps`` maps names of ATTN_TAP_NAMES to CUDA output tensors (empty: the
+        plain forward's launches)."""
+        n, h, w, c = frames.shape
+        unknown = set(taps) - set(ATTN_TAP_NAMES)
+        if unknown:
+            raise KeyError(f"unknown attention taps: {sorted(unknown)}")
+        t = AttnTaps(*[ctypes.c_void_p(_ptr(taps[k]) if k in taps else None) for k in ATTN_TAP_NAMES])
+        check(self.lib.mp_attn_fwd_taps(self.h, _ptr(frames), n, h, w, _ptr(out),
+                                        ctypes.byref(t) if taps else None, ctypes.c_void_p(stream)))
+
+    def attn_path(self, scope: str) -> int:
+        """the MP_PATH_* word of the attention net's conv ``scope`` at the last forward"""
+        return self.info("attn_path:" + scope)
 
     def profile(self, enable: bool) -> None:
         check(self.lib.mp_profile_enable(self.h, 1 if enable else 0))

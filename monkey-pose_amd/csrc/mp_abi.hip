@@ -1547,7 +1547,7 @@ int mp_info(mp_ctx* ctx, const char* key, int64_t* value) {
   return guard([&] {
     if (!ctx || !key || !value) fail(MP_ERR_ARG, "mp_info: null pointer");
     const std::string k(key);
-    if (graph_info(ctx, k, value)) return;
+    if (graph_info(ctx, k, value) || attn_info(ctx, k, value)) return;
     if (k == "output_shape")
       *value = ctx->nout;
     else if (k == "timesteps")

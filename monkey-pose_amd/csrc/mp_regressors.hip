@@ -111,8 +111,9 @@ float* buf(mp_ctx* c, const std::string& name, size_t floats) {
   return d.f();
 }
 
-void conv(mp_ctx* c, const std::string& name, int n, const View& in, const View& out, int stride,
-          hipStream_t st) {
+// launches the conv; returns its launch arguments (the dispatch is a function of them)
+IgemmArgs conv(mp_ctx* c, const std::string& name, int n, const View& in, const View& out, int stride,
+               hipStream_t st) {
   auto it = c->layers.find(name);
   if (it == c->layers.end()) fail(MP_ERR_STATE, "conv layer missing: " + name);
   const auto& L = it->second;
@@ -146,6 +147,7 @@ void conv(mp_ctx* c, const std::string& name, int n, const View& in, const View&
     a.cinp = L.cinp;
   }
   hip_check(L.x3 ? launch_igemm_x3(a, L.w.p, L.wus, st) : launch_igemm_conv(a, st), name.c_str());
+  return a;
 }
 
 void pool(int n, const View& in, const View& out, int mode, hipStream_t st, const float* aff_s = nullptr,
@@ -298,19 +300,30 @@ void hier_forward(mp_ctx* c, const float* depth, int n, int H, int W, float* con
 // attn_model_struct.build (train_cnn_networks_hgru.py:436-525), inference: resize to 128x128,
 // five [conv + relu -> 2x2 max pool -> BN] stages, afc_1 + relu -> BN, afc_out.  The BN of each
 // stage runs in the pool kernel's epilogue, the last one in the afc_1 split-K reduction.
-void attn_forward(mp_ctx* c, const float* frames, int n, int H, int W, float* out, hipStream_t st) {
+void attn_forward(mp_ctx* c, const float* frames, int n, int H, int W, float* out, const mp_attn_taps* tp,
+                  hipStream_t st) {
+  // a tap: copied on the call's stream right after its producer, before the buffer is reused
+  auto tap = [&](float* dst, const float* src, size_t floats, const char* what) {
+    if (dst) hip_check(hipMemcpyAsync(dst, src, floats * sizeof(float), hipMemcpyDeviceToDevice, st), what);
+  };
   float* x = const_cast<float*>(frames);
   if (H != ATTN_SIZE || W != ATTN_SIZE) {
     x = buf(c, "resized", (size_t)n * ATTN_SIZE * ATTN_SIZE);
     hip_check(launch_resize_bilinear(frames, n, H, W, 1, x, ATTN_SIZE, ATTN_SIZE, st), "resize");
   }
+  if (tp) tap(tp->resized, x, (size_t)n * ATTN_SIZE * ATTN_SIZE, "tap resized");
   int h = ATTN_SIZE, w = ATTN_SIZE, cin = 1;
   View cur = V(x, 1, 0, 1, h, w);
   const auto specs = attn_convs();
+  c->attn_conv1_fused = false;
   for (size_t i = 0; i < specs.size(); ++i) {                                                  // 440-476
     const auto& s = specs[i];
     const auto& L = c->layers[s.name];
     const int h2 = same_out(h, 2), w2 = same_out(w, 2);
+    float* const conv_taps[] = {nullptr, tp ? tp->conv2 : nullptr, tp ? tp->conv3 : nullptr,
+                                tp ? tp->conv4 : nullptr, tp ? tp->conv5 : nullptr};
+    float* const pool_taps[] = {tp ? tp->pool1 : nullptr, tp ? tp->pool2 : nullptr, tp ? tp->pool3 : nullptr,
+                                tp ? tp->pool4 : nullptr, tp ? tp->pool5 : nullptr};
     if (i == 0 && h % 2 == 0 && w % 2 == 0) {
       // aconv_1 (1 -> 64, 3x3) + apool_1 + BN in one pass (the hGRU backbone's conv_1 kernel, NHWC
       // out): the 4 MiB-per-frame pre-pool map is never written
@@ -318,6 +331,8 @@ void attn_forward(mp_ctx* c, const float* frames, int n, int H, int W, float* ou
       hip_check(launch_conv1_pool_bn(x, c->raw.at("aconv_1/aconv_1_filters").dev->f(), L.b.f(), L.bn_s.f(),
                                      L.bn_t.f(), pl, n, h, w, st, true),
                 "aconv_1 + apool_1");
+      c->attn_conv1_fused = true;
+      tap(pool_taps[0], pl, (size_t)n * h2 * w2 * 64, "tap pool1");
       cur = V(pl, 64, 0, 64, h2, w2);
       h = h2;
       w = w2;
@@ -325,9 +340,11 @@ void attn_forward(mp_ctx* c, const float* frames, int n, int H, int W, float* ou
       continue;
     }
     float* cv = buf(c, "attn_conv", (size_t)n * h * w * s.cout);
-    conv(c, s.name, n, cur, V(cv, s.cout, 0, s.cout, h, w), 1, st);
+    c->attn_args[s.name] = conv(c, s.name, n, cur, V(cv, s.cout, 0, s.cout, h, w), 1, st);
+    tap(conv_taps[i], cv, (size_t)n * h * w * s.cout, "tap conv");
     float* pl = buf(c, i % 2 ? "attn_pool_b" : "attn_pool_a", (size_t)n * h2 * w2 * s.cout);
     pool(n, V(cv, s.cout, 0, s.cout, h, w), V(pl, s.cout, 0, s.cout, h2, w2), 0, st, L.bn_s.f(), L.bn_t.f());
+    tap(pool_taps[i], pl, (size_t)n * h2 * w2 * s.cout, "tap pool");
     cur = V(pl, s.cout, 0, s.cout, h2, w2);
     h = h2;
     w = w2;
@@ -336,6 +353,7 @@ void attn_forward(mp_ctx* c, const float* frames, int n, int H, int W, float* ou
   float* h1 = buf(c, "attn_fc1", (size_t)n * 1024);
   const auto& F1 = c->layers["afc_1"];
   fcl(c, "afc_1", n, cur.p, h * w * cin, h1, F1.cout, true, st, F1.bn_s.f(), F1.bn_t.f());     // 478-490
+  if (tp) tap(tp->relu1, h1, (size_t)n * F1.cout, "tap relu1");
   fcl(c, "afc_out", n, h1, F1.cout, out, c->layers["afc_out"].cout, false, st);                // 502-503
 }
 
@@ -386,8 +404,32 @@ void pack_matrix(mp_ctx* c, mp_ctx::PackedLayer& L, const float* w, bool x3_ok) 
   }
 }
 
+// mp_info "attn_path:<scope>": the kernel the conv of that scope took at the last forward, from its
+// launch arguments (the launchers switch on the same igemm_x3_path / igemm_conv_path value)
+bool attn_info(mp_ctx* c, const std::string& k, int64_t* v) {
+  if (k.rfind("attn_path:", 0) != 0) return false;
+  if (c->model != MP_MODEL_ATTN) fail(MP_ERR_STATE, "attn_path: context is not an attention model");
+  const std::string scope = strip_scope(k.c_str() + 10);
+  if (scope == "aconv_1" && c->attn_conv1_fused) {
+    IgemmPath p;
+    p.family = MP_PATH_CONV1_POOL_BN;
+    p.pool = 1;
+    *v = p.word();
+    return true;
+  }
+  auto it = c->attn_args.find(scope);
+  if (it == c->attn_args.end()) {
+    if (!c->layers.count(scope) || !c->layers[scope].k) fail(MP_ERR_ARG, "attn_path: no conv layer named " + scope);
+    fail(MP_ERR_STATE, "attn_path: no forward has run yet (run mp_attn_fwd first)");
+  }
+  *v = (c->layers.at(scope).x3 ? igemm_x3_path(it->second) : igemm_conv_path(it->second)).word();
+  return true;
+}
+
 void finalize_regressor(mp_ctx* c) {
   c->layers.clear();
+  c->attn_args.clear();
+  c->attn_conv1_fused = false;
   for (const auto& s : convs_of(c->model)) {
     const auto& w = c->need(s.name + "/" + s.name + "_filters", {s.k, s.k, s.cin, s.cout});
     const auto& b = c->need(s.name + "/" + s.name + "_biases", {s.cout});
@@ -467,7 +509,8 @@ int mp_hier_fwd(mp_ctx* ctx, const float* depth, int64_t n, int64_t h, int64_t w
   });
 }
 
-int mp_attn_fwd(mp_ctx* ctx, const float* frames, int64_t n, int64_t h, int64_t w, float* out, void* stream) {
+int mp_attn_fwd_taps(mp_ctx* ctx, const float* frames, int64_t n, int64_t h, int64_t w, float* out,
+                     const mp_attn_taps* taps, void* stream) {
   return guard([&] {
     if (!ctx || !frames || !out) fail(MP_ERR_ARG, "mp_attn_fwd: null pointer");
     if (ctx->model != MP_MODEL_ATTN) fail(MP_ERR_STATE, "context is not an attention model");
@@ -475,8 +518,12 @@ int mp_attn_fwd(mp_ctx* ctx, const float* frames, int64_t n, int64_t h, int64_t 
     if (n <= 0 || n > (1 << 20) || h < 1 || w < 1 || h > 8192 || w > 8192) fail(MP_ERR_SHAPE, "bad input shape");
     hip_check(hipSetDevice(ctx->device), "hipSetDevice");
     ProfScope ps(ctx, static_cast<hipStream_t>(stream), "attn");
-    attn_forward(ctx, frames, (int)n, (int)h, (int)w, out, static_cast<hipStream_t>(stream));
+    attn_forward(ctx, frames, (int)n, (int)h, (int)w, out, taps, static_cast<hipStream_t>(stream));
   });
+}
+
+int mp_attn_fwd(mp_ctx* ctx, const float* frames, int64_t n, int64_t h, int64_t w, float* out, void* stream) {
+  return mp_attn_fwd_taps(ctx, frames, n, h, w, out, nullptr, stream);
 }
 
 int mp_resize_bilinear(const float* x, int64_t n, int64_t h, int64_t w, int64_t c, int64_t ho, int64_t wo,

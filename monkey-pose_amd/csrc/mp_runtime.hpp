@@ -177,6 +177,10 @@ struct mp_ctx {
   std::map<std::string, DevBuf> ws;            // named activation buffers
   int64_t ws_batch = 0, ws_h = 0, ws_w = 0;
   std::vector<int> head_sizes;                 // outputs: dense {out}; hier {out, P, R, M, I, T}
+  // attention net: each conv's launch arguments at the last forward (mp_info "attn_path:<scope>"), and
+  // whether aconv_1 ran fused with its pool
+  std::map<std::string, IgemmArgs> attn_args;
+  bool attn_conv1_fused = false;
 
   // ---- recorded layer graph (MP_MODEL_GRAPH, mp_graph.hip) ----
   std::shared_ptr<struct GraphState> graph;
@@ -279,6 +283,7 @@ void bn_fold(mp_ctx* c, const std::string& scope, int n, DevBuf& s_out, DevBuf& 
 void finalize_regressor(mp_ctx* c);
 // a conv ([K][Cout]) or fc ([K][N]) weight packed in the context's precision
 void pack_matrix(mp_ctx* c, mp_ctx::PackedLayer& L, const float* w, bool x3_ok);
+bool attn_info(mp_ctx* c, const std::string& key, int64_t* value);    // "attn_*" keys of mp_info
 
 // mp_graph.hip
 void finalize_graph(mp_ctx* c);

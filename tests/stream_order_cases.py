@@ -424,6 +424,46 @@ class AttnCase(Case):
         assert err <= FP32_REL_TOL, err
 
 
+class AttnTapsCase(Case):
+    """mp_attn_fwd_taps on 424 x 512 frames: every tap is a copy on the caller's stream between two launches
+    that reuse its source buffer (attn_conv for conv2 .. conv5, the pool ping-pong), so a copy that ran
+    elsewhere would read the next stage's data"""
+    name = "attn-taps-n2-424x512"
+    covers = ("mp_attn_fwd_taps",)
+    TAP_SHAPES = {"resized": (128, 128, 1), "conv2": (64, 64, 128), "conv3": (32, 32, 256), "conv4": (16, 16, 512),
+                  "conv5": (8, 8, 1024), "pool1": (64, 64, 64), "pool2": (32, 32, 128), "pool3": (16, 16, 256),
+                  "pool4": (8, 8, 512), "pool5": (4, 4, 1024), "relu1": (1024,)}
+    outputs = ("out",) + tuple(TAP_SHAPES)
+
+    def make(self, seed):
+        m = golden_meta()["attn_f424"]
+        return {"frames": _W().synth_frames(m["n"], seed=m["frame_seed"] + 500 * seed, h=m["h"], w=m["w"])}
+
+    def alloc(self):
+        m = golden_meta()["attn_f424"]
+        L = _L()
+        assert tuple(self.TAP_SHAPES) == L.ATTN_TAP_NAMES
+        self.ctx = L.Context(L.MP_MODEL_ATTN, 0)
+        for k, v in _W().attn_synth_weights(seed=m["weight_seed"]).items():
+            self.ctx.set_weight(k, v)
+        self.ctx.finalize(L.dtype_code("fp32_split"))
+        self.out = {"out": _nan((m["n"], 3))}
+        self.out.update({k: _nan((m["n"],) + s) for k, s in self.TAP_SHAPES.items()})
+
+    def invoke(self):
+        taps = {k: v for k, v in self.out.items() if k != "out"}
+        self.ctx.attn_fwd_taps(self.inp["frames"], self.out["out"], taps, _st())
+        return dict(self.out)
+
+    def check_plain(self, A, got):
+        err = rel_inf(got["out"], golden_array("attn_f424", "out"))
+        print(f"{self.name}: plain rel_inf vs the golden float64 vector {err:.3e}")
+        assert err <= FP32_REL_TOL, err
+
+    def close(self):
+        self.ctx.close()
+
+
 def _md(cam=CAM_REF):
     return pkg().monkeydetector.MonkeyDetector(*cam)
 
@@ -883,7 +923,7 @@ def _factories():
           CircuitVarCase, CircuitNhwcFftCase]
     f += [lambda k=k: RegressorCase(k) for k in ("dense", "hier", "dense_hier", "cnn")]
     f += [lambda: RegressorCase("dense", 3), lambda: RegressorCase("dense", use_graph=False),
-          lambda: RegressorCase("hier", use_graph=False), AttnCase]
+          lambda: RegressorCase("hier", use_graph=False), AttnCase, AttnTapsCase]
     f += [lambda: ComCase(False), lambda: ComCase(True)]
     f += [lambda u=u, d=d: DetectCase(u, d) for u in (False, True) for d in (False, True)]
     f += [DetectRawCase, lambda: CropBatchCase(False), lambda: CropBatchCase(True), lambda: CropBatchCase(False, raw=True)]

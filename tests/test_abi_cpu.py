@@ -59,6 +59,29 @@ def test_header_compiles_as_c():
     assert p.returncode == 0, p.stderr
 
 
+def test_tap_structs_match_the_header(tmp_path):
+    """mp_pose_taps and mp_attn_taps: the ctypes field order and offsets are the C compiler's for the header"""
+    L = pkg()._lib
+    lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "monkeypose.h"', 'int main(void){']
+    for c_name, names in (("mp_pose_taps", L.TAP_NAMES), ("mp_attn_taps", L.ATTN_TAP_NAMES)):
+        lines.append(f'printf("{c_name} %zu\\n", sizeof({c_name}));')
+        lines += [f'printf("{c_name}.{n} %zu\\n", offsetof({c_name}, {n}));' for n in names]
+    src = tmp_path / "taps.c"
+    src.write_text("\n".join(lines + ["return 0;}"]) + "\n")
+    exe = tmp_path / "taps"
+    p = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.dirname(HEADER), str(src), "-o", str(exe)],
+                       text=True, capture_output=True)
+    assert p.returncode == 0, p.stderr
+    got = dict(l.split() for l in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines())
+    for c_name, S in (("mp_pose_taps", L.PoseTaps), ("mp_attn_taps", L.AttnTaps)):
+        assert int(got[c_name]) == ctypes.sizeof(S)
+        for n, _ in S._fields_:
+            assert int(got[f"{c_name}.{n}"]) == getattr(S, n).offset, (c_name, n)
+    # the header declares nothing the table lacks
+    body = re.search(r"typedef struct \{([^}]*)\} mp_attn_taps;", open(HEADER).read()).group(1)
+    assert tuple(re.findall(r"float\*\s+(\w+);", body)) == L.ATTN_TAP_NAMES
+
+
 def test_facades_validate_before_gpu():
     import torch
     mp = pkg()
@@ -135,6 +158,7 @@ def test_fwd_opts_struct_size_is_checked():
     L = mp._lib
     lib = L.load()
     assert ctypes.sizeof(L.FwdOpts) == 56 and ctypes.sizeof(L.PoseTaps) == 7 * 8   # the header layouts
+    assert ctypes.sizeof(L.AttnTaps) == 11 * 8
     o = L.fwd_opts(L.MP_HIDDEN_RANDOM, 7, 0)
     o.struct_size = 16
     rc = lib.mp_hgru_pose_fwd_ex(None, None, 1, 128, 128, None, None, ctypes.byref(o), None)
