@@ -87,6 +87,27 @@ enum { MP_MEM_HOST = 0, MP_MEM_DEVICE = 1 };
  *                       the BNs and the fc_1 output stay fp32.  Error ~1e-3 of max|output| on the
  *                       pose (gate 5e-3), a few 1e-3 on the raw circuit state (SURVEY config 4). */
 enum { MP_DTYPE_F32 = 0, MP_DTYPE_F32_SPLIT = 1, MP_DTYPE_F32_FFT = 2, MP_DTYPE_BF16 = 3 };
+/* Magnitude windows.  Every path that is not plain MP_DTYPE_F32 holds its operands as f16 hi + lo behind a
+ * power-of-two scale s: the value times s must stay below f16's 65504 (ceiling), and below 2^-14 / s the
+ * halves are rounded on the grid 2^-24 / s, an absolute error of up to 2^-25 / s per value (floor; times
+ * sum|w| in an output).  tests/test_gpu_magnitude.py runs each path from 2^-24 to the last octave below
+ * 2^15.9 / s on its inputs.
+ *   path                                          scale s              ceiling |a| <      floor 2^-25 / s
+ *   graph runtime convs / FCs (k_igemm, k_fc)     1                    65504              2^-25
+ *   pose conv_2 / conv_3 inputs (k_conv64x3)      16  (BB_ASCALE)      4094               2^-29
+ *   64-channel direct hGRU convs, F32_SPLIT       1024  (ACT_SCALE)    63.97              2^-35
+ *   hGRU 1x1 gates on the FFT paths (gate_x3)     256  (GATE_VSCALE)   255.9              2^-33
+ *   spectra of every FFT conv (k_fft, k_fft4,     1/64  (SPEC_SCALE)   window sum |v|     2^-19 per spectrum
+ *     k_circuit_fft)                                                     < 64 * 65504       entry
+ *   fc_1's planes from the last row kernel        1                    65504              2^-25
+ *   every packed weight tensor                    2^(14 - e),          none: max|w| * s is in [2^13, 2^14);
+ *                                                 frexp(max|w|) = (m, e)  a weight below 2^-17 max|w| is off by
+ *                                                                      up to 2^-25 / s instead of 2^-22 of itself
+ *   MP_DTYPE_BF16 on the six-launch loop          2^-e of max|G|,      p_r's magnitude is taken out, as for a
+ *     (MP_FFT4=0, or MP_BF16_MAPS=0): the         G = p_r's spectrum   weight tensor
+ *     inverse FFTs' f16 intermediates (k_fft)
+ * A weight set times 2^j gives the same packed bits and an output times 2^j, bit for bit.  Outside the window
+ * the result is unspecified (non-finite values may appear); nothing checks it at run time. */
 
 /* library version, (major << 16) | minor */
 int mp_version(void);

@@ -52,6 +52,11 @@ constexpr int FFT_LDS = FX * 4 * FWD_LD;   // complex elements of the block's LD
 // f16 entries (4 B) -- the spectra it feeds are bf16 (8-bit mantissa), so the f16 (11-bit)
 // intermediates add ~1/8 of that rounding, and the halved tile (38.5 KB) lets 3 blocks share a CU
 // instead of 2.  Values stay far inside f16 range (row-FFT outputs <= 64 max|map|, |map| <~ 2).
+// The inverse transforms park values that carry p_r's magnitude instead: those are multiplied by
+// `park`, the power of two that puts max|G| in [0.5, 1) (build_spec_weights), before they are
+// rounded to f16 and by `unpark` = 1 / park (the host's ldexp, a kernel argument like park) when
+// they are read back -- both exact, so the parked bits, and with them the loop's output, do not
+// depend on a power-of-two factor between p_r and gamma / beta.
 template <bool H>
 struct Lds;
 template <>
@@ -197,7 +202,7 @@ __device__ __forceinline__ void fwd_cols_to_S(Lds<BF> T, void* __restrict__ S, i
 // inverse column phase: Y[b][cq][f] -> T[y][c][fx] (rows y < 64).  Direct per-thread loads (72
 // independent 8-byte loads in flight per thread) measured faster than an LDS-staged read.
 template <bool BF>
-__device__ __forceinline__ void inv_cols_to_T(const void* __restrict__ Y, int b, int cq, int tid, Lds<BF> T) {
+__device__ __forceinline__ void inv_cols_to_T(const void* __restrict__ Y, int b, int cq, int tid, Lds<BF> T, float park) {
   if (tid < FX * 4) {
     const int fx = tid >> 2, c = tid & 3;
     const size_t off = (((size_t)b * 16 + cq) * NF + spec_f<BF>(fx, 0)) * 4 + c;
@@ -214,7 +219,10 @@ __device__ __forceinline__ void inv_cols_to_T(const void* __restrict__ Y, int b,
     }
     fft72<1>(v);
 #pragma unroll
-    for (int y = 0; y < 64; ++y) T.set((y * 4 + c) * FX + fx, v[y]);   // rows >= H: unused
+    for (int y = 0; y < 64; ++y) {   // rows >= H: unused
+      if constexpr (BF) T.set((y * 4 + c) * FX + fx, cpx{v[y].x * park, v[y].y * park});
+      else T.set((y * 4 + c) * FX + fx, v[y]);
+    }
   }
 }
 
@@ -417,14 +425,14 @@ __global__ __launch_bounds__(FNT, 3) void fft_fwd3_kernel(const float* __restric
 // inverse 2-D FFT of Y -> the spatial conv result P (C8)
 template <bool BF, bool BM>
 __global__ __launch_bounds__(FNT, BF ? FFT_MINB_BF : FFT_MINB) void fft_inv_kernel(const void* __restrict__ Y, float* __restrict__ P,
-                                                      int H, int W) {
+                                                      int H, int W, float park, float unpark) {
   __shared__ typename Lds<BF>::elem Tbuf[FFT_LDS];
   const Lds<BF> T{Tbuf};
   const int b = fft_block_img(blockIdx.x), cq = fft_block_cq(blockIdx.x);
   const int q = cq >> 1, e0 = 4 * (cq & 1);
   const int tid = threadIdx.x;
   FFT_STAMP_AT(0);
-  inv_cols_to_T<BF>(Y, b, cq, tid, T);
+  inv_cols_to_T<BF>(Y, b, cq, tid, T, park);
   lds_barrier();
   FFT_STAMP_AT(1);
   const int y = tid >> 1, p = tid & 1;
@@ -444,7 +452,8 @@ __global__ __launch_bounds__(FNT, BF ? FFT_MINB_BF : FFT_MINB) void fft_inv_kern
   for (int i = tid; i < H * W; i += FNT) {
     const int yy = i / W, x = i - yy * W;
     const cpx a = T.get((2 * yy) * RLD + x), c = T.get((2 * yy + 1) * RLD + x);
-    map_st4_stream<BM>(P, pp_index(b, q, yy, x, e0, H, W), f32x4{a.x, a.y, c.x, c.y});
+    if constexpr (BF) map_st4_stream<BM>(P, pp_index(b, q, yy, x, e0, H, W), f32x4{a.x, a.y, c.x, c.y} * unpark);
+    else map_st4_stream<BM>(P, pp_index(b, q, yy, x, e0, H, W), f32x4{a.x, a.y, c.x, c.y});
   }
   FFT_STAMP_AT(5);
 }
@@ -456,7 +465,7 @@ __global__ __launch_bounds__(FNT, BF ? FFT_MINB_BF : FFT_MINB) void fft_inv_kern
 // transform's input.  p: the A-epilogue arguments (X, O, vecs; dst = I).
 template <bool BF, bool BM>
 __global__ __launch_bounds__(FNT, BF ? FFT_MINB_BF : FFT_MINB) void fft_inv_a_fwd_kernel(const void* __restrict__ Y, ConvArgs p,
-                                                            void* __restrict__ S) {
+                                                            void* __restrict__ S, float park, float unpark) {
   __shared__ typename Lds<BF>::elem Tbuf[FFT_LDS];
   const Lds<BF> T{Tbuf};
   const int H = p.H, W = p.W;
@@ -478,7 +487,7 @@ __global__ __launch_bounds__(FNT, BF ? FFT_MINB_BF : FFT_MINB) void fft_inv_a_fw
       os[u] = map_ld4<BM>(p.O, oo_index(b, q, yy, x, e0, H, W));
     }
   };
-  inv_cols_to_T<BF>(Y, b, cq, tid, T);
+  inv_cols_to_T<BF>(Y, b, cq, tid, T, park);
   lds_barrier();
   FFT_STAMP_AT(1);
   // (fp32 maps only: the bf16 kernels are held to 168 VGPRs for 3 blocks per CU, and the early set
@@ -525,7 +534,8 @@ __global__ __launch_bounds__(FNT, BF ? FFT_MINB_BF : FFT_MINB) void fft_inv_a_fw
         const int ia = (2 * yy) * RLD + x, ic = (2 * yy + 1) * RLD + x;
         if (yy < H && x < W) {
           const cpx ra = T.get(ia), rc = T.get(ic);
-          const f32x4 pv = {ra.x, ra.y, rc.x, rc.y};
+          f32x4 pv = {ra.x, ra.y, rc.x, rc.y};
+          if constexpr (BF) pv = pv * unpark;
           f32x4 iv;
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
@@ -1410,7 +1420,7 @@ hipError_t device_absmax(const float* x, size_t n, float* out) {
 
 size_t fft_weight_bytes() { return (size_t)NF * 2 * 16 * 64 * sizeof(f16x8); }
 
-hipError_t build_spec_weights(const float* w, int ks, void* Gx, float* unscale, bool bf, bool cls_major) {
+hipError_t build_spec_weights(const float* w, int ks, void* Gx, float* unscale, bool bf, bool cls_major, float* park) {
   cpx* G = nullptr;
   unsigned* mx = nullptr;
   hipError_t e = hipMalloc(&G, (size_t)NF * 4096 * sizeof(cpx));
@@ -1425,6 +1435,14 @@ hipError_t build_spec_weights(const float* w, int ks, void* Gx, float* unscale, 
   }
   unsigned bits = 0;
   if (e == hipSuccess) e = hipMemcpy(&bits, mx, sizeof(unsigned), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && park) {   // max|G| to [0.5, 1): the scale of the inverse transforms' f16 parking
+    float m;
+    std::memcpy(&m, &bits, sizeof m);
+    int ex = 0;
+    if (m > 0.f && std::isfinite(m)) std::frexp(m, &ex);
+    // park and 1 / park both normal floats (a denormal or overflowing spectrum parks at the nearest such scale)
+    *park = std::ldexp(1.0f, -std::min(std::max(ex, -120), 120));
+  }
   if (e == hipSuccess && bf) {
     *unscale = 1.0f;
     hipLaunchKernelGGL(spec_pack_bf_kernel, dim3(NF * 16 * 64 / 256), dim3(256), 0, 0, G, static_cast<uint4*>(Gx));
@@ -1461,15 +1479,16 @@ hipError_t launch_fft_fwd(const float* act, void* S, int B, int H, int W, hipStr
   return hipGetLastError();
 }
 
-hipError_t launch_fft_inv_a_fwd(const void* Y, const ConvArgs& a, void* S, int B, hipStream_t st, bool bf) {
+hipError_t launch_fft_inv_a_fwd(const void* Y, const ConvArgs& a, void* S, int B, hipStream_t st, bool bf, float park) {
+  const float unpark = 1.0f / park;   // park is a power of two in [2^-120, 2^120]: exact
   if (!bf && !fy_major<false>() && B <= lfft_maxb())
     hipLaunchKernelGGL(lfft_inv_a_fwd_kernel, dim3(B * 32), dim3(LF_NT), 0, st, Y, a, S);
   else if (bf && fft_bf16_maps())
-    hipLaunchKernelGGL((fft_inv_a_fwd_kernel<true, true>), dim3(B * 16), dim3(FNT), 0, st, Y, a, S);
+    hipLaunchKernelGGL((fft_inv_a_fwd_kernel<true, true>), dim3(B * 16), dim3(FNT), 0, st, Y, a, S, park, unpark);
   else if (bf)
-    hipLaunchKernelGGL((fft_inv_a_fwd_kernel<true, false>), dim3(B * 16), dim3(FNT), 0, st, Y, a, S);
+    hipLaunchKernelGGL((fft_inv_a_fwd_kernel<true, false>), dim3(B * 16), dim3(FNT), 0, st, Y, a, S, park, unpark);
   else
-    hipLaunchKernelGGL((fft_inv_a_fwd_kernel<false, false>), dim3(B * 16), dim3(FNT), 0, st, Y, a, S);
+    hipLaunchKernelGGL((fft_inv_a_fwd_kernel<false, false>), dim3(B * 16), dim3(FNT), 0, st, Y, a, S, park, unpark);
   return hipGetLastError();
 }
 
@@ -1492,15 +1511,16 @@ hipError_t launch_spec_gemm(const void* S, const void* Gx, void* Y, int B, float
   return hipGetLastError();
 }
 
-hipError_t launch_fft_inv(const void* Y, float* P, int B, int H, int W, hipStream_t st, bool bf) {
+hipError_t launch_fft_inv(const void* Y, float* P, int B, int H, int W, hipStream_t st, bool bf, float park) {
+  const float unpark = 1.0f / park;   // park is a power of two in [2^-120, 2^120]: exact
   if (!bf && !fy_major<false>() && B <= lfft_maxb())
     hipLaunchKernelGGL(lfft_inv_kernel, dim3(B * 32), dim3(LF_NT), 0, st, Y, P, H, W);
   else if (bf && fft_bf16_maps())
-    hipLaunchKernelGGL((fft_inv_kernel<true, true>), dim3(B * 16), dim3(FNT), 0, st, Y, P, H, W);
+    hipLaunchKernelGGL((fft_inv_kernel<true, true>), dim3(B * 16), dim3(FNT), 0, st, Y, P, H, W, park, unpark);
   else if (bf)
-    hipLaunchKernelGGL((fft_inv_kernel<true, false>), dim3(B * 16), dim3(FNT), 0, st, Y, P, H, W);
+    hipLaunchKernelGGL((fft_inv_kernel<true, false>), dim3(B * 16), dim3(FNT), 0, st, Y, P, H, W, park, unpark);
   else
-    hipLaunchKernelGGL((fft_inv_kernel<false, false>), dim3(B * 16), dim3(FNT), 0, st, Y, P, H, W);
+    hipLaunchKernelGGL((fft_inv_kernel<false, false>), dim3(B * 16), dim3(FNT), 0, st, Y, P, H, W, park, unpark);
   return hipGetLastError();
 }
 

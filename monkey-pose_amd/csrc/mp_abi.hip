@@ -225,7 +225,8 @@ void finalize_circuit(mp_ctx* c, const std::vector<float>* outs, const std::vect
     c->spec_g.alloc(fft_weight_bytes());
     // the general loop (has_var) runs launch_fft_fwd / _spec_gemm / _fft_inv: six-launch weights
     c->fft4 = !c->has_var && fft4_enabled() && (c->dtype == MP_DTYPE_F32_FFT || (bf && fft_bf16_maps()));
-    hip_check(build_spec_weights(it->second.dev->f(), c->ssf, c->spec_g.p, &c->p_unscale, bf, c->fft4), "p_r spectrum");
+    hip_check(build_spec_weights(it->second.dev->f(), c->ssf, c->spec_g.p, &c->p_unscale, bf, c->fft4, &c->p_park),
+              "p_r spectrum");
     c->or_x3.alloc(gate_x3_bytes());
     c->ir_x3.alloc(gate_x3_bytes());
     hip_check(pack_gate_x3(c->need("contextual_circuit/o_r", {1, 1, 64, 64}).dev->f(), c->or_x3.p, &c->or_us, bf),
@@ -534,7 +535,7 @@ void six_launch(mp_ctx* c, void* S, void* Y, float* P, const ConvArgs& a, const 
       hip_check(launch_spec_gemm(S, c->spec_g.p, Y, n, c->p_unscale, st, bf), "spec_gemm");
     }
     ProfScope ps(c, st, "inv_a_fwd");
-    hip_check(launch_fft_inv_a_fwd(Y, a, S, n, st, bf), "fft_inv_a_fwd");
+    hip_check(launch_fft_inv_a_fwd(Y, a, S, n, st, bf, c->p_park), "fft_inv_a_fwd");
   }
   ProfScope pb(c, st, "conv15_b");
   {
@@ -543,7 +544,7 @@ void six_launch(mp_ctx* c, void* S, void* Y, float* P, const ConvArgs& a, const 
   }
   {
     ProfScope ps(c, st, "fft_inv");
-    hip_check(launch_fft_inv(Y, P, n, b.H, b.W, st, bf), "fft_inv");
+    hip_check(launch_fft_inv(Y, P, n, b.H, b.W, st, bf, c->p_park), "fft_inv");
   }
   ProfScope ps(c, st, "epi_b");
   hip_check(launch_spec_epi_b(b, P, c->or_x3.p, c->or_us, c->ir_x3.p, c->ir_us, n, st, bf), "B epilogue");

@@ -71,13 +71,15 @@ size_t fft_spec_bytes(int B);      // one spectrum buffer (S or Y) for B images
 size_t fft_weight_bytes();         // expanded split spectral weights
 // HWIO [ks][ks][64][64] -> packed split spectral weights (synchronous, finalize time)
 // cls_major: the four-step loop's class-major frequency order (k_fft4.hip)
-hipError_t build_spec_weights(const float* w, int ks, void* Gx, float* unscale, bool bf = false, bool cls_major = false);
+hipError_t build_spec_weights(const float* w, int ks, void* Gx, float* unscale, bool bf = false, bool cls_major = false,
+                              float* park = nullptr);
 hipError_t launch_fft_fwd(const float* act, void* S, int B, int H, int W, hipStream_t st, bool bf = false);
 hipError_t launch_spec_gemm(const void* S, const void* Gx, void* Y, int B, float unscale, hipStream_t st,
                             bool bf = false);
-hipError_t launch_fft_inv(const void* Y, float* P, int B, int H, int W, hipStream_t st, bool bf = false);
+hipError_t launch_fft_inv(const void* Y, float* P, int B, int H, int W, hipStream_t st, bool bf = false, float park = 1.f);
 // P1 = IFFT(Y); I = A-epilogue(P1) -> a.dst; S = FFT(I)   (the A half-step tail + B half-step head)
-hipError_t launch_fft_inv_a_fwd(const void* Y, const ConvArgs& a, void* S, int B, hipStream_t st, bool bf = false);
+hipError_t launch_fft_inv_a_fwd(const void* Y, const ConvArgs& a, void* S, int B, hipStream_t st, bool bf = false,
+                                float park = 1.f);
 // B epilogue with f16x3 gate GEMMs (FFT path); gate weights packed by pack_gate_x3 (synchronous)
 size_t gate_x3_bytes();
 hipError_t pack_gate_x3(const float* g, void* out, float* unscale, bool bf = false);

@@ -121,6 +121,7 @@ struct mp_ctx {
   int ssf = 15, timesteps = 8, nout = 0, fc1_in = 0, fc1_out = 0;
   int dtype = MP_DTYPE_F32;
   float p_unscale = 1.f;   // F32_SPLIT / F32_FFT: 1 / (weight scale * activation or spectrum scale)
+  float p_park = 1.f;      // bf16 six-launch loop: the power of two its inverse FFTs park their f16 values at
   std::vector<float> rho;
   DevBuf conv1_w, conv1_b, bn0_s, bn0_t;
   DevBuf conv1_ig;          // conv_1 packed for the generic igemm (conv1 tap of mp_hgru_pose_fwd_taps)

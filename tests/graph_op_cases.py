@@ -377,6 +377,34 @@ def conv_graph(c: ConvCase):
     return g, [g.pool(y) if c.pool else y]
 
 
+def sibling_graph(cs, couts, H=5, W=5):
+    """(recorder, source, siblings, their pools): an 8 -> cs 1x1 source conv and its 1x1 siblings"""
+    G = pkg()._graph
+    g = G.GraphRecorder(H, W, 8)
+    src = g.conv(g.input, 8, cs, "src", k=1)
+    sibs = [g.conv(src, cs, co, f"s{i}", k=1) for i, co in enumerate(couts)]
+    pools = [g.pool(s) for s in sibs]                 # each consumer reads its slice in place
+    return g, src, sibs, pools
+
+
+def fc_graph(K):
+    """(recorder, outputs, {head: (N, relu folded)}): every FC head of FC_HEADS on one K-wide input"""
+    G = pkg()._graph
+    g = G.GraphRecorder(1, 1, K)
+    if K == 32768:
+        return g, [g.fc(g.input, K, 8, "f8")], {"f8": (8, False)}
+    f5, f8 = g.fc(g.input, K, 5, "f5"), g.fc(g.input, K, 8, "f8")
+    cat = g.concat([f5, f8])                                   # rank-2: ldo = 13, coff = 5
+    f32r = g.relu(g.fc(g.input, K, 32, "f32r"))
+    f32 = g.fc(g.input, K, 32, "f32")
+    f69 = g.fc(g.input, K, 69, "f69")
+    f130r = g.relu(g.fc(g.input, K, 130, "f130r"))
+    f130 = g.fc(g.input, K, 130, "f130")
+    return g, [cat, f32r, f32, f69, f130r, f130], {"f5": (5, False), "f8": (8, False), "f32r": (32, True),
+                                                   "f32": (32, False), "f69": (69, False), "f130r": (130, True),
+                                                   "f130": (130, False)}
+
+
 def run_conv_case(name, dtype):
     """One CONV_CASES row at one dtype, at every batch size: (reported path, fused pools,
     max err / bound)."""

@@ -28,6 +28,7 @@ import pytest
 
 import graph_op_cases as C
 from graph_op_cases import U, bound, conv_expected, conv_terms, forward, layer_w, layer_weights, make_ctx, ratio
+from graph_op_cases import fc_graph as _fc_graph, sibling_graph as _sibling_graph
 
 pytestmark = pytest.mark.gpu
 
@@ -180,15 +181,6 @@ def test_conv1_pool_fusion(case, hw, dtype):
 
 
 # ----------------------------------------------------------------------- planner: 1x1 siblings
-def _sibling_graph(cs, couts, H=5, W=5):
-    G = _G()
-    g = G.GraphRecorder(H, W, 8)
-    src = g.conv(g.input, 8, cs, "src", k=1)
-    sibs = [g.conv(src, cs, co, f"s{i}", k=1) for i, co in enumerate(couts)]
-    pools = [g.pool(s) for s in sibs]                 # each consumer reads its slice in place
-    return g, src, sibs, pools
-
-
 @pytest.mark.parametrize("dtype", ["fp32_split", "fp32"])
 @pytest.mark.parametrize("case", [c[0] for c in C.SIBLING_CASES])
 def test_1x1_siblings(case, dtype, monkeypatch):
@@ -280,23 +272,6 @@ def test_pool_between_concat_slices(avg):
 
 
 # --------------------------------------------------------------------------------------- FC
-def _fc_graph(K):
-    G = _G()
-    g = G.GraphRecorder(1, 1, K)
-    if K == 32768:
-        return g, [g.fc(g.input, K, 8, "f8")], {"f8": (8, False)}
-    f5, f8 = g.fc(g.input, K, 5, "f5"), g.fc(g.input, K, 8, "f8")
-    cat = g.concat([f5, f8])                                   # rank-2: ldo = 13, coff = 5
-    f32r = g.relu(g.fc(g.input, K, 32, "f32r"))
-    f32 = g.fc(g.input, K, 32, "f32")
-    f69 = g.fc(g.input, K, 69, "f69")
-    f130r = g.relu(g.fc(g.input, K, 130, "f130r"))
-    f130 = g.fc(g.input, K, 130, "f130")
-    return g, [cat, f32r, f32, f69, f130r, f130], {"f5": (5, False), "f8": (8, False), "f32r": (32, True),
-                                                   "f32": (32, False), "f69": (69, False), "f130r": (130, True),
-                                                   "f130": (130, False)}
-
-
 @pytest.mark.parametrize("dtype", ["fp32_split", "fp32", "bf16"])
 @pytest.mark.parametrize("K", C.FC_K)
 def test_fc(K, dtype):
