@@ -277,6 +277,10 @@ hipError_t launch_eval_summary(const void* state, int J, int T, double* out, hip
 size_t png_work_bytes(int64_t n, int h, int w);
 hipError_t launch_png_encode(const uint8_t* rgb, int64_t n, int h, int w, uint8_t* out, int64_t out_stride,
                              int64_t* sizes, void* work, hipStream_t st);
+// k_png16.hip (PNG files from 16-bit depth frames; the byte rule is png16_rule.hpp)
+size_t png16_work_bytes(int64_t n, int h, int w);
+hipError_t launch_png16_encode(const uint16_t* frames, int64_t n, int h, int w, uint8_t* out, int64_t out_stride,
+                               int64_t* sizes, void* work, hipStream_t st);
 // k_pngdec.hip (PNG files to pixels; the rule is pngdec_rule.hpp)
 size_t pngdec_work_bytes(int64_t n, int h, int w, int format, int64_t file_stride);
 hipError_t launch_png_decode(const uint8_t* files, int64_t file_stride, const int64_t* sizes, int64_t n, int h, int w,

@@ -12,6 +12,10 @@ The other direction is ``decode_png`` (include/monkeypose_pngdec.h, csrc/pngdec_
 (``mp_png_decode_host``, the same rule on one thread, no zlib, no PIL).  ``decode_png_files`` packs,
 uploads and decodes a list of files or paths; ``load_depth_map`` is ``loadDepthMap`` of the
 reference's importer.
+
+``encode_depth_png`` writes such depth frames (include/monkeypose_png16.h, csrc/png16_rule.hpp): uint16
+[n, h, w] to 16-bit grayscale files with per-row filters and a dynamic Huffman code per band, on the
+device (``mp_png16_encode_dev``) or on the host by the same rule; ``save_depth_maps`` writes the files.
 """
 from __future__ import annotations
 
@@ -47,6 +51,21 @@ _PNGDEC_SIGS = {
                                          ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 }
+# every function include/monkeypose_png16.h declares
+_PNG16_SIGS = {
+    "mp_png16_bound": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64]),
+    "mp_png16_work_bytes": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int64]),
+    "mp_png16_band_rows": (ctypes.c_int, [ctypes.c_int64]),
+    "mp_png16_band_count": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64]),
+    "mp_png16_encode_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    "mp_png16_encode_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                           ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p]),
+    "mp_png16_band_stats_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                ctypes.c_void_p]),
+}
+STAT_INTS = 9      # MP_PNG16_STAT_INTS: form, five filter counts, matches, distance symbols, tree depth
 FORMATS = {"gray16": 0, "gray8": 1, "rgb8": 2}
 MAX_FILE_STRIDE = 1 << 30
 STATUS_NAMES = {0: "decoded", 1: "container", 2: "CRC", 3: "unsupported", 4: "h, w or format is not the call's",
@@ -59,7 +78,7 @@ _BUFFERS = {}      # (n, h, w, device) -> (buf, sizes, work): reused by the next
 def _lib_png():
     lib = _lib.load()
     if not getattr(lib, "_png_bound", False):
-        for name, (res, args) in list(_PNG_SIGS.items()) + list(_PNGDEC_SIGS.items()):
+        for name, (res, args) in list(_PNG_SIGS.items()) + list(_PNGDEC_SIGS.items()) + list(_PNG16_SIGS.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         lib._png_bound = True
@@ -156,6 +175,124 @@ def png_files(buf, sizes):
     sz = sizes.cpu().numpy()
     host = buf[:, :int(sz.max())].cpu().numpy()
     return [host[i, :int(s)].tobytes() for i, s in enumerate(sz)]
+
+
+# ------------------------------------------------------------------------------------------ depth frames
+_DEPTH_BUFFERS = {}    # (n, h, w, device) -> {stream: (buf, sizes, work)}
+
+
+def _depth_shape(shape):
+    if len(shape) != 3:
+        raise ValueError(f"frames must be [n, h, w], got {tuple(shape)}")
+    n, h, w = (int(v) for v in shape)
+    if not (1 <= n <= MAX_N and 1 <= h <= MAX_HW and 1 <= w <= MAX_HW):
+        raise ValueError(f"frames must have 1 <= n <= {MAX_N} and 1 <= h, w <= {MAX_HW}, got n = {n}, h = {h}, w = {w}")
+    return n, h, w
+
+
+def depth_png_bound(h, w):
+    """Bytes of the largest file ``encode_depth_png`` writes for an h x w frame (every band stored)."""
+    h, w = int(h), int(w)
+    if not (1 <= h <= MAX_HW and 1 <= w <= MAX_HW):
+        raise ValueError(f"1 <= h, w <= {MAX_HW}, got h = {h}, w = {w}")
+    return int(_lib_png().mp_png16_bound(h, w))
+
+
+def depth_band_plan(h, w):
+    """(rows of a band, number of bands) of an h x w depth frame: the plan the files' IDAT chunks follow."""
+    depth_png_bound(h, w)
+    lib = _lib_png()
+    return int(lib.mp_png16_band_rows(int(w))), int(lib.mp_png16_band_count(int(h), int(w)))
+
+
+def depth_band_stats(frames):
+    """What the rule did with each band of the numpy uint16 frames [n, h, w]: int32 [n, bands, 9] --
+    the form chosen (0 stored, 1 fixed, 2 dynamic), the rows that took each of the five filters, the
+    matches, the distinct distance symbols and the depth of the Huffman tree before the 15-bit limit
+    (``mp_png16_band_stats_host``)."""
+    if not isinstance(frames, np.ndarray) or frames.dtype != np.uint16:
+        raise TypeError("frames must be a numpy uint16 array")
+    n, h, w = _depth_shape(frames.shape)
+    lib = _lib_png()
+    a = np.ascontiguousarray(frames)
+    stats = np.zeros((n, int(lib.mp_png16_band_count(h, w)), STAT_INTS), np.int32)
+    _lib.check(lib.mp_png16_band_stats_host(a.ctypes.data_as(ctypes.c_void_p), n, h, w,
+                                            stats.ctypes.data_as(ctypes.c_void_p)))
+    return stats
+
+
+def encode_depth_png(frames, stream=None, out=None):
+    """16-bit grayscale PNG files of the depth frames ``frames`` [n, h, w] uint16 -> ``(buf [n, bound]
+    uint8, sizes [n] int64)``: frame i's file is ``buf[i, :sizes[i]]`` and ``bound = depth_png_bound(h, w)``.
+    ``decode_png`` (and PIL, and the importer's ``loadDepthMap``) read them back bit for bit.
+
+    A CUDA (ROCm) ``torch.uint16`` tensor is encoded on the device, on ``stream`` (default: the current
+    one), without a host wait; the pair is CUDA tensors, reused by the next call of the same shape on
+    that device and stream unless ``out = (buf, sizes)`` is given (contiguous CUDA tensors, ``buf`` [n, >= bound]
+    uint8).  A numpy array is encoded on the host by the same rule (csrc/png16_rule.hpp: per-row
+    filters, bands of whole rows, a stored, fixed or dynamic Huffman block a band) and the pair is
+    numpy arrays.  ``png_files`` turns either pair into ``bytes``."""
+    import torch
+    lib = _lib_png()
+    if isinstance(frames, np.ndarray):
+        if frames.dtype != np.uint16:
+            raise TypeError(f"frames must be uint16, got {frames.dtype}")
+        n, h, w = _depth_shape(frames.shape)
+        if out is not None:
+            raise ValueError("out= is for CUDA input")
+        a = np.ascontiguousarray(frames)
+        bound = int(lib.mp_png16_bound(h, w))
+        buf, sizes = np.zeros((n, bound), np.uint8), np.zeros(n, np.int64)
+        _lib.check(lib.mp_png16_encode_host(a.ctypes.data_as(ctypes.c_void_p), n, h, w,
+                                            buf.ctypes.data_as(ctypes.c_void_p), bound,
+                                            sizes.ctypes.data_as(ctypes.c_void_p)))
+        return buf, sizes
+    if not isinstance(frames, torch.Tensor):
+        raise TypeError("frames must be a CUDA (ROCm) uint16 tensor or a numpy uint16 array")
+    if frames.dtype != torch.uint16:
+        raise TypeError(f"frames must be uint16, got {frames.dtype}")
+    n, h, w = _depth_shape(frames.shape)
+    if not frames.is_cuda:
+        raise TypeError("frames must be a CUDA (ROCm) tensor (host frames: pass a numpy array)")
+    dev = frames.device
+    bound = int(lib.mp_png16_bound(h, w))
+    stp = _lib.current_stream(dev) if stream is None else stream
+    key = (n, h, w, dev)
+    if key not in _DEPTH_BUFFERS:
+        _DEPTH_BUFFERS.clear()      # one shape's buffers at a time, as encode_png keeps its
+        _DEPTH_BUFFERS[key] = {}
+    held = _DEPTH_BUFFERS[key].get(stp)
+    if held is None:                # .. and one set per stream: two streams' calls share no scratch
+        held = _DEPTH_BUFFERS[key][stp] = (
+            torch.empty((n, bound), dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.int64, device=dev),
+            torch.empty(int(lib.mp_png16_work_bytes(n, h, w)), dtype=torch.uint8, device=dev))
+    buf, sizes, work = held
+    if out is not None:
+        buf, sizes = out
+        if not (isinstance(buf, torch.Tensor) and buf.is_cuda and buf.dtype == torch.uint8 and buf.dim() == 2
+                and buf.shape[0] == n and buf.shape[1] >= bound and buf.stride(1) == 1 and buf.device == dev):
+            raise ValueError(f"out[0] must be a CUDA uint8 tensor [{n}, >= {bound}] with unit column stride")
+        if not (isinstance(sizes, torch.Tensor) and sizes.is_cuda and sizes.dtype == torch.int64
+                and tuple(sizes.shape) == (n,) and sizes.is_contiguous() and sizes.device == dev):
+            raise ValueError(f"out[1] must be a contiguous CUDA int64 tensor [{n}]")
+    src = frames.detach().contiguous()
+    _lib.check(lib.mp_png16_encode_dev(ctypes.c_void_p(src.data_ptr()), n, h, w, ctypes.c_void_p(buf.data_ptr()),
+                                       int(buf.stride(0)) if n > 1 else max(int(buf.stride(0)), bound),
+                                       ctypes.c_void_p(sizes.data_ptr()), ctypes.c_void_p(work.data_ptr()),
+                                       ctypes.c_void_p(stp)))
+    return buf, sizes
+
+
+def save_depth_maps(paths, frames):
+    """One 16-bit grayscale PNG file per frame: ``frames`` [n, h, w] uint16 (a CUDA tensor is encoded on
+    the device, a numpy array on the host) to the n ``paths``.  The inverse of ``load_depth_map`` and
+    ``decode_png_files``."""
+    paths = list(paths)
+    if len(paths) != int(frames.shape[0]):
+        raise ValueError(f"{len(paths)} paths for {int(frames.shape[0])} frames")
+    for path, data in zip(paths, png_files(*encode_depth_png(frames))):
+        with open(path, "wb") as f:
+            f.write(data)
 
 
 # ------------------------------------------------------------------------------------------ decoding
