@@ -1,16 +1,17 @@
-// The host encoder of png16_rule.hpp: the rule on one thread, written the plain way -- a row's five
-// filters one after the other, a position's matches by comparing bytes, one token after the other,
-// the checksums byte by byte.  Plain C++ (no HIP), so that tests/png16_rule_main.cpp builds it with the
-// host sanitizers; mp_png16.hip wraps it for the library, and the kernels of k_png16.hip are compared
-// with it byte for byte.
+// The host encoder of png16_rule.hpp on png_host.hpp's frame: the rule on one thread, written the plain
+// way -- a row's five filters one after the other, one token after the other, the three forms' sizes
+// and the dynamic block's header.  Plain C++ (no HIP), so that tests/png16_rule_main.cpp builds it with
+// the host sanitizers; mp_png16.hip wraps it for the library, and the kernels of k_png16.hip are
+// compared with it byte for byte.
 #pragma once
-#include <cstring>
 #include <stdexcept>
-#include <vector>
 
 #include "png16_rule.hpp"
+#include "png_host.hpp"
 
 namespace mppng16h {
+
+using mppngh::BitWriter;
 
 // what mp_png16_band_stats_host reports of a band (include/monkeypose_png16.h)
 constexpr int STAT_INTS = 9;
@@ -19,52 +20,13 @@ struct BandStats {
 };
 static_assert(sizeof(BandStats) == STAT_INTS * 4, "nine int32 a band");
 
-struct CrcTable {
-  uint32_t t[256];
-  CrcTable() {
-    for (uint32_t i = 0; i < 256; ++i) t[i] = mppng::crc_table_entry(i);
-  }
-};
-
-inline uint32_t crc32_of(const uint8_t* p, size_t n) {
-  static const CrcTable tab;
-  uint32_t c = 0xffffffffu;
-  for (size_t i = 0; i < n; ++i) c = tab.t[(c ^ p[i]) & 0xffu] ^ (c >> 8);
-  return ~c;
-}
-
-inline void put_be32(uint8_t* p, uint32_t v) {
-  p[0] = (uint8_t)(v >> 24);
-  p[1] = (uint8_t)(v >> 16);
-  p[2] = (uint8_t)(v >> 8);
-  p[3] = (uint8_t)v;
-}
-
-// length || type || data || crc at p -> the bytes written
-inline size_t put_chunk(uint8_t* p, const char* type, const uint8_t* data, size_t n) {
-  put_be32(p, (uint32_t)n);
-  std::memcpy(p + 4, type, 4);
-  if (n) std::memcpy(p + 8, data, n);
-  put_be32(p + 8 + n, crc32_of(p + 4, 4 + n));
-  return n + mppng::CHUNK_BYTES;
-}
-
-struct BitWriter {
-  std::vector<uint8_t>& v;
-  uint64_t acc = 0;
-  int nb = 0;
-  void put(uint32_t val, int n) {     // n <= 32
-    acc |= (uint64_t)val << nb;
-    nb += n;
-    while (nb >= 8) {
-      v.push_back((uint8_t)acc);
-      acc >>= 8;
-      nb -= 8;
-    }
-  }
-  void align() {
-    if (nb) put(0, 8 - nb);
-  }
+// the 16-bit grayscale format, for the file's frame on the host and on the device
+struct Gray16 {
+  static constexpr int BIT_DEPTH = 16, COLOUR_TYPE = 0;
+  MP_PNG_HD static constexpr int row_bytes(int w) { return mppng16::row_bytes(w); }
+  static constexpr int band_rows(int w) { return mppng16::band_rows(w); }
+  static constexpr int band_count(int h, int w) { return mppng16::band_count(h, w); }
+  static constexpr int band_len(int h, int w, int k) { return mppng16::band_len(h, w, k); }
 };
 
 // rows [r0, r0 + nr) of the frame, filtered, to raw (nr * row_bytes(w)); filters[f] += rows that took f
@@ -106,14 +68,8 @@ inline void encode_band(const uint8_t* a, int len, int w, bool last, std::vector
   int64_t fixed_bits = 0, extra_bits = 0;
   int matches = 0;
   for (int p = 0; p < len;) {
-    int bl = 0, bd = 0;
-    for (int c = 0; c < nc; ++c) {
-      const int d = cd[c];
-      if (d > p) continue;
-      int L = 0;
-      while (L < R::MAX_MATCH && p + L < len && a[p + L] == a[p + L - d]) ++L;
-      if (L > bl || (L == bl && d < bd)) bl = L, bd = d;
-    }
+    const mppngh::Match m = mppngh::best_match(a, len, p, cd, nc);
+    const int bl = m.len, bd = m.dist;
     if (bl >= R::MIN_MATCH) {
       int eb, db;
       uint32_t ev;
@@ -154,10 +110,7 @@ inline void encode_band(const uint8_t* a, int len, int w, bool last, std::vector
   const size_t at = out.size();
   BitWriter bw{out};
   if (form == R::FORM_STORED) {
-    const uint8_t head[5] = {0, (uint8_t)len, (uint8_t)(len >> 8), (uint8_t)~len, (uint8_t)(~len >> 8)};
-    out.insert(out.end(), head, head + 5);
-    out.insert(out.end(), a, a + len);
-    out.push_back(last ? 1 : 0);
+    mppngh::put_stored_block(out, a, len, last);
   } else {
     if (form == R::FORM_FIXED) {
       bw.put(mppng::FIXED_HEAD, mppng::BLOCK_HEAD_BITS);
@@ -199,8 +152,7 @@ inline void encode_band(const uint8_t* a, int len, int w, bool last, std::vector
     bw.put(last ? 1u : 0u, mppng::BLOCK_HEAD_BITS);
     bw.align();
   }
-  const uint8_t empty[4] = {0, 0, 0xff, 0xff};
-  out.insert(out.end(), empty, empty + 4);
+  mppngh::put_empty_block(out);
   // the size the rule's formulas gave is the size written
   const int want = form == R::FORM_STORED ? stored_b : form == R::FORM_FIXED ? fixed_b : dynamic_b;
   if ((int)(out.size() - at) != want) throw std::logic_error("png16: a band's bytes are not its formula's");
@@ -208,39 +160,13 @@ inline void encode_band(const uint8_t* a, int len, int w, bool last, std::vector
 
 // one frame [h][w] -> its file at out (bound(h, w) bytes are enough); stats: band_count entries or null
 inline size_t encode_image(const uint16_t* frame, int h, int w, uint8_t* out, BandStats* stats) {
-  namespace R = mppng16;
-  static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
-  uint8_t* p = out;
-  std::memcpy(p, sig, 8);
-  p += 8;
-  uint8_t ihdr[13];
-  put_be32(ihdr, (uint32_t)w);
-  put_be32(ihdr + 4, (uint32_t)h);
-  ihdr[8] = 16, ihdr[9] = 0, ihdr[10] = 0, ihdr[11] = 0, ihdr[12] = 0;
-  p += put_chunk(p, "IHDR", ihdr, 13);
-
-  const int rb = R::row_bytes(w), rows = R::band_rows(w), nb = R::band_count(h, w);
-  std::vector<uint8_t> raw((size_t)rows * rb), data;
-  uint32_t A = 1, B = 0;
-  for (int k = 0; k < nb; ++k) {
-    const int len = R::band_len(h, w, k);
-    BandStats* st = stats ? stats + k : nullptr;
-    if (st) std::memset(st, 0, sizeof *st);
-    filter_rows(frame, w, k * rows, len / rb, raw.data(), st ? st->filters : nullptr);
-    for (int i = 0; i < len; ++i) {
-      A = (A + raw[i]) % mppng::ADLER_MOD;
-      B = (B + A) % mppng::ADLER_MOD;
-    }
-    data.clear();
-    if (k == 0) data.push_back(0x78), data.push_back(0x01);
-    encode_band(raw.data(), len, w, k == nb - 1, data, st);
-    p += put_chunk(p, "IDAT", data.data(), data.size());
-  }
-  uint8_t ad[4];
-  put_be32(ad, (B << 16) | A);
-  p += put_chunk(p, "IDAT", ad, 4);
-  p += put_chunk(p, "IEND", nullptr, 0);
-  return (size_t)(p - out);
+  if (stats) std::memset(stats, 0, (size_t)mppng16::band_count(h, w) * sizeof *stats);
+  return mppngh::encode_file<Gray16>(
+      h, w, out,
+      [&](int k, int r0, int nr, uint8_t* raw) { filter_rows(frame, w, r0, nr, raw, stats ? stats[k].filters : nullptr); },
+      [&](int k, const uint8_t* a, int len, bool last, std::vector<uint8_t>& data) {
+        encode_band(a, len, w, last, data, stats ? stats + k : nullptr);
+      });
 }
 
 }  // namespace mppng16h

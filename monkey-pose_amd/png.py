@@ -72,7 +72,6 @@ STATUS_NAMES = {0: "decoded", 1: "container", 2: "CRC", 3: "unsupported", 4: "h,
                 5: "deflate / zlib stream", 6: "Adler-32", 7: "filter byte"}
 _SIGNATURE = b"\x89PNG\r\n\x1a\n"
 
-_BUFFERS = {}      # (n, h, w, device) -> (buf, sizes, work): reused by the next call of the same shape
 
 
 def _lib_png():
@@ -92,6 +91,72 @@ def _shape(shape):
     if not (1 <= n <= MAX_N and 1 <= h <= MAX_HW and 1 <= w <= MAX_HW):
         raise ValueError(f"rgb must have 1 <= n <= {MAX_N} and 1 <= h, w <= {MAX_HW}, got n = {n}, h = {h}, w = {w}")
     return n, h, w
+
+
+class _Format:
+    """What one encoder differs from the other in: the input's name in messages (and how they call a host
+    input), its dtype (numpy's; torch's has the same name), its shape check, and the library's four
+    functions ``<prefix>_bound``, ``_work_bytes``, ``_encode_host`` and ``_encode_dev``."""
+
+    def __init__(self, word, host_word, dtype, shape, prefix):
+        self.word, self.host_word, self.dtype, self.shape, self.prefix = word, host_word, np.dtype(dtype), shape, prefix
+        self.buffers = {}           # (n, h, w, device) -> {stream: (buf, sizes, work)}
+
+
+def _encode(fmt, x, stream, out):
+    """``encode_png`` and ``encode_depth_png``: ``x`` of the format ``fmt`` -> ``(buf, sizes)``"""
+    import torch
+    lib = _lib_png()
+    fn = {k: getattr(lib, f"{fmt.prefix}_{k}") for k in ("bound", "work_bytes", "encode_host", "encode_dev")}
+    if isinstance(x, np.ndarray):
+        if x.dtype != fmt.dtype:
+            raise TypeError(f"{fmt.word} must be {fmt.dtype}, got {x.dtype}")
+        n, h, w = fmt.shape(x.shape)
+        if out is not None:
+            raise ValueError("out= is for CUDA input")
+        a = np.ascontiguousarray(x)
+        bound = int(fn["bound"](h, w))
+        buf, sizes = np.zeros((n, bound), np.uint8), np.zeros(n, np.int64)
+        _lib.check(fn["encode_host"](a.ctypes.data_as(ctypes.c_void_p), n, h, w, buf.ctypes.data_as(ctypes.c_void_p),
+                                     bound, sizes.ctypes.data_as(ctypes.c_void_p)))
+        return buf, sizes
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{fmt.word} must be a CUDA (ROCm) {fmt.dtype} tensor or a numpy {fmt.dtype} array")
+    if x.dtype != getattr(torch, fmt.dtype.name):
+        raise TypeError(f"{fmt.word} must be {fmt.dtype}, got {x.dtype}")
+    n, h, w = fmt.shape(x.shape)
+    if not x.is_cuda:
+        raise TypeError(f"{fmt.word} must be a CUDA (ROCm) tensor ({fmt.host_word}: pass a numpy array)")
+    dev = x.device
+    bound = int(fn["bound"](h, w))
+    stp = _lib.current_stream(dev) if stream is None else stream
+    key = (n, h, w, dev)
+    if key not in fmt.buffers:
+        fmt.buffers.clear()         # one shape's buffers at a time, as the pipelines keep theirs
+        fmt.buffers[key] = {}
+    held = fmt.buffers[key].get(stp)
+    if held is None:                # .. and one set per stream: two streams' calls share no scratch
+        held = fmt.buffers[key][stp] = (
+            torch.empty((n, bound), dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.int64, device=dev),
+            torch.empty(int(fn["work_bytes"](n, h, w)), dtype=torch.uint8, device=dev))
+    buf, sizes, work = held
+    if out is not None:
+        buf, sizes = out
+        if not (isinstance(buf, torch.Tensor) and buf.is_cuda and buf.dtype == torch.uint8 and buf.dim() == 2
+                and buf.shape[0] == n and buf.shape[1] >= bound and buf.stride(1) == 1 and buf.device == dev):
+            raise ValueError(f"out[0] must be a CUDA uint8 tensor [{n}, >= {bound}] with unit column stride")
+        if not (isinstance(sizes, torch.Tensor) and sizes.is_cuda and sizes.dtype == torch.int64
+                and tuple(sizes.shape) == (n,) and sizes.is_contiguous() and sizes.device == dev):
+            raise ValueError(f"out[1] must be a contiguous CUDA int64 tensor [{n}]")
+    src = x.detach().contiguous()
+    _lib.check(fn["encode_dev"](ctypes.c_void_p(src.data_ptr()), n, h, w, ctypes.c_void_p(buf.data_ptr()),
+                                int(buf.stride(0)) if n > 1 else max(int(buf.stride(0)), bound),
+                                ctypes.c_void_p(sizes.data_ptr()), ctypes.c_void_p(work.data_ptr()),
+                                ctypes.c_void_p(stp)))
+    return buf, sizes
+
+
+_RGB = _Format("rgb", "a host picture", np.uint8, _shape, "mp_png")
 
 
 def png_bound(h, w):
@@ -114,57 +179,11 @@ def encode_png(rgb, stream=None, out=None):
     picture i's file is ``buf[i, :sizes[i]]`` and ``bound = png_bound(h, w)``.
 
     A CUDA (ROCm) tensor is encoded on the device, on ``stream`` (default: the current one), without a
-    host wait; the pair is CUDA tensors, reused by the next call of the same shape on that device
-    unless ``out = (buf, sizes)`` is given (contiguous CUDA tensors, ``buf`` [n, >= bound] uint8).  A
+    host wait; the pair is CUDA tensors, reused by the next call of the same shape on that device and
+    stream unless ``out = (buf, sizes)`` is given (contiguous CUDA tensors, ``buf`` [n, >= bound] uint8).  A
     numpy array is encoded on the host by the same rule and the pair is numpy arrays.  ``png_files``
     turns either pair into ``bytes``."""
-    import torch
-    lib = _lib_png()
-    if isinstance(rgb, np.ndarray):
-        if rgb.dtype != np.uint8:
-            raise TypeError(f"rgb must be uint8, got {rgb.dtype}")
-        n, h, w = _shape(rgb.shape)
-        if out is not None:
-            raise ValueError("out= is for CUDA input")
-        a = np.ascontiguousarray(rgb)
-        bound = int(lib.mp_png_bound(h, w))
-        buf, sizes = np.zeros((n, bound), np.uint8), np.zeros(n, np.int64)
-        _lib.check(lib.mp_png_encode_host(a.ctypes.data_as(ctypes.c_void_p), n, h, w,
-                                          buf.ctypes.data_as(ctypes.c_void_p), bound,
-                                          sizes.ctypes.data_as(ctypes.c_void_p)))
-        return buf, sizes
-    if not isinstance(rgb, torch.Tensor):
-        raise TypeError("rgb must be a CUDA (ROCm) uint8 tensor or a numpy uint8 array")
-    if rgb.dtype != torch.uint8:
-        raise TypeError(f"rgb must be uint8, got {rgb.dtype}")
-    n, h, w = _shape(rgb.shape)
-    if not rgb.is_cuda:
-        raise TypeError("rgb must be a CUDA (ROCm) tensor (a host picture: pass a numpy array)")
-    dev = rgb.device
-    bound = int(lib.mp_png_bound(h, w))
-    key = (n, h, w, dev)
-    held = _BUFFERS.get(key)
-    if held is None:
-        _BUFFERS.clear()            # one shape's buffers at a time, as the pipelines keep theirs
-        held = _BUFFERS[key] = (torch.empty((n, bound), dtype=torch.uint8, device=dev),
-                                torch.empty(n, dtype=torch.int64, device=dev),
-                                torch.empty(int(lib.mp_png_work_bytes(n, h, w)), dtype=torch.uint8, device=dev))
-    buf, sizes, work = held
-    if out is not None:
-        buf, sizes = out
-        if not (isinstance(buf, torch.Tensor) and buf.is_cuda and buf.dtype == torch.uint8 and buf.dim() == 2
-                and buf.shape[0] == n and buf.shape[1] >= bound and buf.stride(1) == 1 and buf.device == dev):
-            raise ValueError(f"out[0] must be a CUDA uint8 tensor [{n}, >= {bound}] with unit column stride")
-        if not (isinstance(sizes, torch.Tensor) and sizes.is_cuda and sizes.dtype == torch.int64
-                and tuple(sizes.shape) == (n,) and sizes.is_contiguous() and sizes.device == dev):
-            raise ValueError(f"out[1] must be a contiguous CUDA int64 tensor [{n}]")
-    src = rgb.detach().contiguous()
-    stp = _lib.current_stream(dev) if stream is None else stream
-    _lib.check(lib.mp_png_encode_dev(ctypes.c_void_p(src.data_ptr()), n, h, w, ctypes.c_void_p(buf.data_ptr()),
-                                     int(buf.stride(0)) if n > 1 else max(int(buf.stride(0)), bound),
-                                     ctypes.c_void_p(sizes.data_ptr()), ctypes.c_void_p(work.data_ptr()),
-                                     ctypes.c_void_p(stp)))
-    return buf, sizes
+    return _encode(_RGB, rgb, stream, out)
 
 
 def png_files(buf, sizes):
@@ -178,9 +197,6 @@ def png_files(buf, sizes):
 
 
 # ------------------------------------------------------------------------------------------ depth frames
-_DEPTH_BUFFERS = {}    # (n, h, w, device) -> {stream: (buf, sizes, work)}
-
-
 def _depth_shape(shape):
     if len(shape) != 3:
         raise ValueError(f"frames must be [n, h, w], got {tuple(shape)}")
@@ -188,6 +204,9 @@ def _depth_shape(shape):
     if not (1 <= n <= MAX_N and 1 <= h <= MAX_HW and 1 <= w <= MAX_HW):
         raise ValueError(f"frames must have 1 <= n <= {MAX_N} and 1 <= h, w <= {MAX_HW}, got n = {n}, h = {h}, w = {w}")
     return n, h, w
+
+
+_DEPTH = _Format("frames", "host frames", np.uint16, _depth_shape, "mp_png16")
 
 
 def depth_png_bound(h, w):
@@ -232,55 +251,7 @@ def encode_depth_png(frames, stream=None, out=None):
     uint8).  A numpy array is encoded on the host by the same rule (csrc/png16_rule.hpp: per-row
     filters, bands of whole rows, a stored, fixed or dynamic Huffman block a band) and the pair is
     numpy arrays.  ``png_files`` turns either pair into ``bytes``."""
-    import torch
-    lib = _lib_png()
-    if isinstance(frames, np.ndarray):
-        if frames.dtype != np.uint16:
-            raise TypeError(f"frames must be uint16, got {frames.dtype}")
-        n, h, w = _depth_shape(frames.shape)
-        if out is not None:
-            raise ValueError("out= is for CUDA input")
-        a = np.ascontiguousarray(frames)
-        bound = int(lib.mp_png16_bound(h, w))
-        buf, sizes = np.zeros((n, bound), np.uint8), np.zeros(n, np.int64)
-        _lib.check(lib.mp_png16_encode_host(a.ctypes.data_as(ctypes.c_void_p), n, h, w,
-                                            buf.ctypes.data_as(ctypes.c_void_p), bound,
-                                            sizes.ctypes.data_as(ctypes.c_void_p)))
-        return buf, sizes
-    if not isinstance(frames, torch.Tensor):
-        raise TypeError("frames must be a CUDA (ROCm) uint16 tensor or a numpy uint16 array")
-    if frames.dtype != torch.uint16:
-        raise TypeError(f"frames must be uint16, got {frames.dtype}")
-    n, h, w = _depth_shape(frames.shape)
-    if not frames.is_cuda:
-        raise TypeError("frames must be a CUDA (ROCm) tensor (host frames: pass a numpy array)")
-    dev = frames.device
-    bound = int(lib.mp_png16_bound(h, w))
-    stp = _lib.current_stream(dev) if stream is None else stream
-    key = (n, h, w, dev)
-    if key not in _DEPTH_BUFFERS:
-        _DEPTH_BUFFERS.clear()      # one shape's buffers at a time, as encode_png keeps its
-        _DEPTH_BUFFERS[key] = {}
-    held = _DEPTH_BUFFERS[key].get(stp)
-    if held is None:                # .. and one set per stream: two streams' calls share no scratch
-        held = _DEPTH_BUFFERS[key][stp] = (
-            torch.empty((n, bound), dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.int64, device=dev),
-            torch.empty(int(lib.mp_png16_work_bytes(n, h, w)), dtype=torch.uint8, device=dev))
-    buf, sizes, work = held
-    if out is not None:
-        buf, sizes = out
-        if not (isinstance(buf, torch.Tensor) and buf.is_cuda and buf.dtype == torch.uint8 and buf.dim() == 2
-                and buf.shape[0] == n and buf.shape[1] >= bound and buf.stride(1) == 1 and buf.device == dev):
-            raise ValueError(f"out[0] must be a CUDA uint8 tensor [{n}, >= {bound}] with unit column stride")
-        if not (isinstance(sizes, torch.Tensor) and sizes.is_cuda and sizes.dtype == torch.int64
-                and tuple(sizes.shape) == (n,) and sizes.is_contiguous() and sizes.device == dev):
-            raise ValueError(f"out[1] must be a contiguous CUDA int64 tensor [{n}]")
-    src = frames.detach().contiguous()
-    _lib.check(lib.mp_png16_encode_dev(ctypes.c_void_p(src.data_ptr()), n, h, w, ctypes.c_void_p(buf.data_ptr()),
-                                       int(buf.stride(0)) if n > 1 else max(int(buf.stride(0)), bound),
-                                       ctypes.c_void_p(sizes.data_ptr()), ctypes.c_void_p(work.data_ptr()),
-                                       ctypes.c_void_p(stp)))
-    return buf, sizes
+    return _encode(_DEPTH, frames, stream, out)
 
 
 def save_depth_maps(paths, frames):

@@ -33,6 +33,8 @@ import stream_order_cases as SO
 from helpers import ROOT, pkg
 
 PNG16_HEADER = os.path.join(ROOT, "include", "monkeypose_png16.h")
+GOLDEN_DIR = os.path.join(ROOT, "tests", "golden", "png16")
+GOLDEN = ("1x1", "3x1", "const-20x30", "no-match-4x20", "byte-order", "five-filters")
 FORM_STORED, FORM_FIXED, FORM_DYNAMIC = 0, 1, 2
 S_FORM, S_FILTERS, S_MATCHES, S_DIST, S_DEPTH = 0, slice(1, 6), 6, 7, 8
 

@@ -203,8 +203,12 @@ class PngCase(SO.Case):
     outputs = ("png", "sizes")
     SHAPE = (2, 40, 50, 3)
 
+    def __init__(self, draw=0):
+        self.draw = draw            # another draw of the pictures: the second of two concurrent calls
+        self.name = f"png_encode-{draw}" if draw else "png_encode"
+
     def make(self, seed):
-        rng = np.random.default_rng(910 + seed)
+        rng = np.random.default_rng(910 + seed + 100 * self.draw)
         a = (rng.integers(0, 6, self.SHAPE) * 50).astype(np.uint8)
         a[:, 10:20] = a[:, 9:10]
         return {"rgb": a}

@@ -55,6 +55,26 @@ def test_two_calls_agree_and_buffers_are_reused():
     assert np.array_equal(C.read_png(f1[0], 424, 512), C.picture("overlay-jet")[0])
 
 
+class _N3Case(C.PngCase):
+    SHAPE = (3, 20, 30, 3)                 # png_cases' n3
+
+
+@pytest.mark.gpu
+def test_two_encodes_on_two_streams_are_both_right():
+    """stream_order_cases' hazards (late producer, immediate consumer, early release, back to back) for
+    two calls of different pictures of one shape at once, each on a stream of its own into buffers of
+    its own: the scratch is per stream too (tests/test_gpu_png16.py's test, with RGB pictures)"""
+    preps = [SO.Prepared(_N3Case(draw)) for draw in (0, 1)]
+    try:
+        assert not np.array_equal(preps[0].A["rgb"], preps[1].A["rgb"])
+        streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+        report = SO.check_hazards(preps, streams, "two fresh streams")
+        assert len(report) == 2 and all("conclusive" in r for r in report)
+    finally:
+        for p in preps:
+            p.close()
+
+
 @pytest.mark.gpu
 def test_a_file_does_not_depend_on_its_batch():
     P = C.P()

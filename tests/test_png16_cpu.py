@@ -5,7 +5,9 @@ every file decodes to its frame bit for bit with three decoders that share no co
 two size bounds hold, refusals come before anything is written, and the rule alone -- built as a host
 program with the address and undefined-behaviour sanitizers -- writes the library's bytes."""
 import ctypes
+import hashlib
 import io
+import json
 import os
 import re
 import shutil
@@ -120,6 +122,19 @@ def test_a_file_does_not_depend_on_its_batch():
     x = C.frames("n3")
     for i, f in enumerate(_files("n3")):
         assert C.P().png_files(*C.P().encode_depth_png(x[i:i + 1])) == [f]
+
+
+def test_host_files_equal_the_recorded_bytes():
+    """every case's size and SHA-256 (tests/golden/png16/digests.json), and the whole files where they are kept"""
+    with open(os.path.join(C.GOLDEN_DIR, "digests.json")) as f:
+        table = json.load(f)
+    assert sorted(table) == sorted(C.NAMES)
+    for name in C.NAMES:
+        got = [{"sha256": hashlib.sha256(f).hexdigest(), "size": len(f)} for f in _files(name)]
+        assert got == table[name], name
+    for name in C.GOLDEN:
+        with open(os.path.join(C.GOLDEN_DIR, name + ".png"), "rb") as f:
+            assert _files(name) == [f.read()], name
 
 
 # ------------------------------------------------------------------------------------------ sizes

@@ -5,7 +5,9 @@ equal committed files byte for byte.  Also the refusals, and the new header's in
 as C99, the library exports what it declares, png.py's ctypes table is its function list, and its
 stream prototypes are the ones tests/test_gpu_png.py orders."""
 import ctypes
+import hashlib
 import io
+import json
 import os
 import re
 import subprocess
@@ -147,6 +149,19 @@ def test_refusals():
 def test_golden_files(name):
     with open(os.path.join(C.GOLDEN_DIR, name + ".png"), "rb") as f:
         assert _files(name)[0] == f.read()
+
+
+def test_host_files_equal_the_recorded_bytes():
+    """every case's size and SHA-256 (tests/golden/png/digests.json), and the whole files where they are kept"""
+    with open(os.path.join(C.GOLDEN_DIR, "digests.json")) as f:
+        table = json.load(f)
+    assert sorted(table) == sorted(C.NAMES)
+    for name in C.NAMES:
+        got = [{"sha256": hashlib.sha256(f).hexdigest(), "size": len(f)} for f in _files(name)]
+        assert got == table[name], name
+    for name in C.GOLDEN:
+        with open(os.path.join(C.GOLDEN_DIR, name + ".png"), "rb") as f:
+            assert _files(name) == [f.read()], name
 
 
 # ------------------------------------------------------------------------------------------ the header
